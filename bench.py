@@ -18,7 +18,10 @@ then VGA for the rank's sources and one RCCL all-gather of the 7 float columns.
 Inputs (grid state + occluder pieces) are resident in HBM before the timed region; value =
 filled cells / step time (max over ranks).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 1000|256]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 1000|256] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line; --dump-outputs DIR also saves
+what the last timed step computed (DIR/<name>.npy), and --full adds the seeded CPU baseline (cpu_baseline,
+vs_cpu_baseline), which runs after the timed steps and takes about half a minute at 1000^2.
 The default workload is BASELINE.json configs[2]: the 1000 x 1000 synthetic grid (1001^2 cells),
 makeGraph + VGA global (radius n) on one MI355X; configs[1] (256^2) is --grid 256.
     torchrun --nproc-per-node N bench.py --gpus N ...      (one process per GPU, RCCL)
@@ -218,6 +221,23 @@ def cpu_baseline(region, lines, spacing, fill, g, budget_s, seed=2026, stepdepth
     return rec
 
 
+DUMP_BUDGET = 64 * 10 ** 6   # bytes, all --dump-outputs files together
+
+
+def dump_outputs(outdir, arrays, seed=2026):
+    """--dump-outputs: each array as outdir/<name>.npy in float32.  An array over its equal share of DUMP_BUDGET
+    is cut to a fixed seeded sample of its rows (ascending row order; the same rows on every run of the
+    same workload), so two builds can be compared file by file."""
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_BUDGET // len(arrays)
+    for name, a in sorted(arrays.items()):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        rows = share // max(a[0].nbytes, 1) if len(a) else 0
+        if len(a) > rows:
+            a = a[np.sort(np.random.default_rng(seed).choice(len(a), size=rows, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -236,6 +256,12 @@ def main():
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="unused (the CPU sample is fixed: S=200 / S=20)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dump-out", default=None, help="rank 0 saves the gathered [N][7] VGA columns (.npy)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 saves what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB "
+                         "in all): the VGA columns or the step depths, and the makeGraph attributes")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline (cpu_baseline, vs_cpu_baseline) after the timed steps; a plain "
+                         "run only sets up, warms up, times the steps and prints the result line")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -553,13 +579,17 @@ def main():
                        "stepdepth_cells_relaxed": stats.get("sd_cells_relaxed"),
                        "stepdepth_algorithmic_bytes": vga_bytes,
                        "stepdepth_reached_cells": int((sd_out[0][:, 0] >= 0).sum())})
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             rec["cpu_baseline"] = cpu_baseline(region, lines, 1.0, fill, g, args.cpu_budget, stepdepth=stepdepth,
                                                N=N, sd_cell=sd_cell)
             rec["vs_cpu_baseline"] = rec["value"] / rec["cpu_baseline"]["value"]
         print(json.dumps(rec), flush=True)
         if args.dump_out and out_full is not None:
             np.save(args.dump_out, out_full.cpu().numpy())
+        if args.dump_outputs:
+            res = sd_out[0] if stepdepth else out_full.cpu().numpy()
+            dump_outputs(args.dump_outputs, {"metric_step_depth" if stepdepth else "vga_global": res,
+                                             "makegraph_attrs": g.copy(runs=False)["attrs"]})
     if dist_on:
         dist.destroy_process_group()
 

@@ -21,7 +21,7 @@ if [ "${PART:-2}" = 2 ]; then
   cp $OUT/r${RD}_pmc.json profiles/r${RD}_pmc.json   # the bench below reads it
   [ $rc = 0 ] && timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 && \
   t0=$(date +%s.%N) && \
-  timeout -k 10 600 python -u bench.py --gpus 1 --steps ${STEPS:-10} --warmup ${WARMUP:-2} > $OUT/bench.log 2> $OUT/bench_progress.txt && \
+  timeout -k 10 600 python -u bench.py --gpus 1 --steps ${STEPS:-10} --warmup ${WARMUP:-2} --full > $OUT/bench.log 2> $OUT/bench_progress.txt && \
   t1=$(date +%s.%N) && echo "bench wall s: $(python -c "print($t1 - $t0)")" >> $OUT/bench_progress.txt
   rc=$?
   tail -5 $OUT/pmc2.log; tail -2 $OUT/smoke.log; grep '^{' $OUT/bench.log | cut -c1-300; tail -1 $OUT/bench_progress.txt
@@ -31,7 +31,7 @@ else
   rc=$?
   python3 scripts/pmc_summary.py gpurun_out/$T/pmc5 "$W5" $OUT/r${RD}_pmc.json > $OUT/pmc5_summary.log 2>&1
   cp $OUT/r${RD}_pmc.json profiles/r${RD}_pmc.json
-  [ $rc = 0 ] && timeout -k 10 400 python -u bench.py --gpus 1 --config 5 --steps 2 --warmup 1 > $OUT/bench5.log 2> $OUT/bench5_progress.txt && \
+  [ $rc = 0 ] && timeout -k 10 400 python -u bench.py --gpus 1 --config 5 --steps 2 --warmup 1 --full > $OUT/bench5.log 2> $OUT/bench5_progress.txt && \
   timeout -k 10 600 python -u -m pytest -x -v --timeout 500 --timeout-method thread -m gpu \
     tests/test_gpu_scale.py -k "2000_vga_sources" > $OUT/vga2000_wide_tests.log 2>&1
   rc=$?
