@@ -632,6 +632,35 @@ struct Vga : Mode {
         });
         std::cout << " ok" << std::endl;
     }
+    // runVga THRU_VISION branch (runmethods.cpp:255-257) -> VGAThroughVision::run (vgathroughvision.cpp:27-104):
+    // one column "Through vision", set for every row, not locked, displayed (:92-101).  -s makes no difference.
+    void run_thruvision(const Args& a, Perf& perf, Document& d, Context& C, LoadedMap& m) {
+        // the gate-counting side branch (vgathroughvision.cpp:61-74) is not part of the accelerated path
+        int32_t ncols = 0;
+        check(dmx_chunk_info(m.chunk, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ncols, nullptr, nullptr));
+        for (int i = 0; i < ncols; i++) {
+            char name[256] = {0};
+            check(dmx_chunk_column(m.chunk, i, name, (int)sizeof(name), nullptr, nullptr));
+            if (!std::strcmp(name, "__Internal_Gate"))
+                throw RuntimeException("The map has a column __Internal_Gate: through vision with gate counting is not "
+                                       "part of the accelerated path");
+            // getOrInsertColumn (:92) keeps an existing column's lock and statistics, which setValue then adds to
+            // (attributetable.cpp:328-336): not reproduced
+            if (!std::strcmp(name, "Through vision"))
+                throw RuntimeException("The map already has a column Through vision: running it again is not part of "
+                                       "the accelerated path");
+        }
+        std::cout << " ok\nAnalysing graph..." << std::flush;
+        std::vector<float> out((size_t)m.nnodes, 0.0f);
+        timed(perf, "Run VGA", [&] { check(dmx_vga_thruvision(C.ctx, m.g, 0, -1, out.data(), nullptr)); });
+        std::cout << " ok\nWriting out result..." << std::flush;
+        timed(perf, "Writing graph", [&] {
+            m.column("Through vision", out.data(), nullptr, false, true);
+            d.put_displayed(m.bytes(), false);
+            write_document(a.out, d);
+        });
+        std::cout << " ok" << std::endl;
+    }
     void run(const Args& a, Perf& perf) override {
         Document d;
         // the reference's loadGraph reads and parses the whole file: the chunk decode and the upload count in
@@ -651,8 +680,12 @@ struct Vga : Mode {
             run_metric(a, perf, d, C, m);
             return;
         }
+        if (mode == THRU) {
+            run_thruvision(a, perf, d, C, m);
+            return;
+        }
         if (mode != VISIBILITY)
-            throw RuntimeException("Only -vm visibility, metric and angular are part of the accelerated path");
+            throw RuntimeException("Only -vm visibility, metric, angular and thruvision are part of the accelerated path");
         double r = -1.0;
         if (global) {
             if (radius != "n") {

@@ -36,6 +36,7 @@
 #include "kernels/fill.hip"
 #include "kernels/vstep.hip"
 #include "kernels/vga_ordered.hip"
+#include "kernels/thruvision.hip"
 
 using namespace dmx;
 
@@ -681,6 +682,7 @@ int dmx_ctx_last_timing(dmx_ctx* c, double* mk, double* vga) {
 #include "api/shard.hip"
 #include "api/vga_global.hip"
 #include "api/vga_other.hip"
+#include "api/thruvision.hip"
 #include "api/stepdepth.hip"
 #include "api/chunk.hip"
 #include "api/graphfile.hip"

@@ -35,6 +35,13 @@ constexpr int kVgaSourceChunk = 1;
 constexpr int kVgaDoAlpha = 15;
 constexpr int kVgaDoShortList = 16;
 
+// ---- VGA through vision (thruvision.hip)
+// side of the LDS window of 32-bit counters around the source (variant B; 0 would select variant A, global
+// atomics only).  64^2 x 4 B = 16 KiB lets eight workgroups share a CU's LDS (profiles/thruvision_ab.jsonl)
+constexpr int kTvWindow = 64;
+// the largest window the DMX_TV_WINDOW hook accepts (128^2 counters; next to the kernel's static 3 KiB)
+constexpr int kTvWindowMaxBytes = 64 * 1024;
+
 // ---- memory: optional summaries are built only within a share of the free device memory, so a graph
 // that fills the GPU still runs (on the slower exact path that needs no summary)
 // tile rows (tvis / ftvis) and partial-tile masks on narrow grids: a quarter of the free memory

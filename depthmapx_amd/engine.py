@@ -111,7 +111,7 @@ class Context:
                 "vga_hard_cells", "vga_hard_certain", "vga_topdown_cycles", "vga_b_tiles", "vga_b_cells", "vga_tt_tiles", "vga_c_busy", "vga_c_scan", "vga_c_spec", "vga_n_spec", "vga_tt_pruned", "vga_b_row_cycles", "vga_b_cell_tiles",
                 "vga_b_cell_cycles", "vga_b_ext_cells", "mk_depth_steps", "mk_chunks", "mk_reruns", "vga_pmask_loads", "vga_pmask_cells", "vga_pmask_bytes",
                 "vga_order_reruns", "vga_sym_scatter_us", "vga_prep_flags", "vga_tile_rows_bytes", "vga_scan_bytes",
-                "vga_asym_nodes"]
+                "vga_asym_nodes", "tv_lines", "tv_pixel_steps", "tv_window"]
         # vga_c_scan, vga_c_spec, vga_b_row_cycles and vga_b_cell_cycles stay 0: the kernel no longer reads
         # the clock per hard cell or per tile (2.6 % of the 1000^2 VGA); the per-phase clocks remain
         d = {k: int(v) for k, v in zip(keys, out)}
@@ -363,6 +363,18 @@ class Graph:
         N.check(N.lib().dmx_vga_local(self.ctx.h, self.h, int(bool(gates_only)), int(src_begin), int(src_end),
                                       N.ptr(out)))
         return out
+
+    def vga_through_vision(self, src_begin=0, src_end=-1, counts=False):
+        """VGA -vm thruvision (VGAThroughVision::run, vgamodules/vgathroughvision.cpp:27-104) on the GPU:
+        [N] float32 "Through vision", the count the sources [src_begin, src_end) add to every cell (every row
+        is written).  counts=True also returns the same numbers as int64, which sum exactly over disjoint
+        source ranges."""
+        n = self.info()["nnodes"]
+        out = np.zeros(n, dtype=np.float32)
+        cnt = np.zeros(n, dtype=np.int64) if counts else None
+        N.check(N.lib().dmx_vga_thruvision(self.ctx.h, self.h, int(src_begin), int(src_end), N.ptr(out),
+                                           N.ptr(cnt)))
+        return (out, cnt) if counts else out
 
     def metric_step_depth(self, points=None, cells=None):
         """STEPDEPTH -sdt metric (dm_runmethods::runStepDepth, depthmapXcli/runmethods.cpp:735-778):

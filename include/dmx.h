@@ -67,7 +67,7 @@ typedef int32_t (*dmx_progress_fn)(void* user, int32_t phase, int64_t done, int6
 int dmx_ctx_set_progress(dmx_ctx* ctx, dmx_progress_fn fn, void* user, double interval_s);
 /* Request cancellation of the operation running on ctx (callable from any thread).  The request is
  * consumed by the operation that observes it; one made while no operation runs cancels the next
- * makegraph, VGA-global or step-depth (metric, angular, visual) call at its first poll -- before that
+ * makegraph, VGA-global, through-vision or step-depth (metric, angular, visual) call at its first poll -- before that
  * call writes any output.  VGA local / metric / angular do not poll (a pending request waits). */
 int dmx_ctx_cancel(dmx_ctx* ctx);
 /* Wall time of the kernels of the last makegraph / vga call, measured with HIP events on the
@@ -87,7 +87,9 @@ int dmx_ctx_last_timing(dmx_ctx* ctx, double* makegraph_s, double* vga_s);
  * memory-dependent VGA preparation the last tile search ran with (bits: 0 scan order, 1 scan order released for
  * the partial-tile masks, 2 tile-visibility rows, 3 fully-seen rows, 4 tile-to-tile rows, 5 partial-tile masks,
  * 6 row summaries, 7 asymmetric mode), [41] bytes of tile-visibility rows held, [42] bytes of the scan order
- * held, [43] asymmetric mode: nodes whose runs differ from the reference graph (dmx_graph_set_drawing).  n <= 48. */
+ * held, [43] asymmetric mode: nodes whose runs differ from the reference graph (dmx_graph_set_drawing), [44] lines
+ * the last through-vision call walked, [45] its pixel steps, [46] its accumulation variant (0 global atomics,
+ * else the side of the LDS window).  n <= 48. */
 int dmx_ctx_last_stats(dmx_ctx* ctx, int64_t* out, int n);
 
 /* The sources the last makeGraph swept a second time (graph node indices, in the order the passes listed
@@ -229,6 +231,21 @@ int dmx_vga_angular(dmx_ctx* ctx, dmx_graph* g, double radius, int gates_only, i
  * sources and neighbourhoods of <= 1 cell).  The two tile bitmaps per source live in LDS up to ~780^2
  * cells and in per-workgroup HBM slices above that (no grid-size limit). */
 int dmx_vga_local(dmx_ctx* ctx, dmx_graph* g, int gates_only, int64_t src_begin, int64_t src_end, float* out);
+/* ---- VGA through vision (GPU) --------------------------------------------------------------- */
+/* MetaGraph::analyseGraph(OUTPUT_THRU_VISION) -> VGAThroughVision().run (salalib/mgraph.cpp:366-368,
+ * vgamodules/vgathroughvision.cpp:27-104): for every source node in [src_begin, src_end) (src_end < 0: all)
+ * and every cell of the source's runs, the line from that cell to the source is walked with
+ * PixelBase::quickPixelateLine (salalib/spacepix.cpp:218-270, the same sequence of FP64 adds) and every pixel
+ * between its two ends counts once.  The graph must hold every node (DMX_ERR_STATE otherwise).  Unlike the
+ * per-source analyses EVERY row of out (host [N], node order) is written: the count the sources of the range
+ * add to that cell, as float ("Through vision").  counts (optional, host [N]) receives the same numbers as
+ * integers, so the results of disjoint source ranges (one per GPU) can be summed exactly.  Merge links play no
+ * part; context-filled sources are not skipped.  The reference counts in an int (Point::m_misc): a total
+ * above INT32_MAX returns DMX_ERR_UNSUPPORTED instead of wrapping.  The gate-counting side branch
+ * (vgathroughvision.cpp:61-74, maps with a column __Internal_Gate) is not part of this call.  Progress and
+ * cancel as in dmx_vga_global. */
+int dmx_vga_thruvision(dmx_ctx* ctx, dmx_graph* g, int64_t src_begin, int64_t src_end,
+                       float* out /* host [N] */, int64_t* counts /* host [N], optional */);
 /* Multi-GPU share of the VGA preparation (no reference counterpart: the reference prepares nothing;
  * this splits our own O(runs) pre-passes).  Every rank holds the whole graph; the per-node scatters
  * (in-set hash sums, tile-visibility rows) then run over nodes [node_begin, node_end)

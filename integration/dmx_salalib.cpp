@@ -239,4 +239,34 @@ bool vgaVisualGlobal(PointMap& map, Communicator* comm, double radius, bool gate
     return load(map, serialize(c.p));
 }
 
+// VGAThroughVision::run (vgathroughvision.cpp:27-104).  The reference path keeps: the gate-counting side branch
+// (a column __Internal_Gate, :61-74) and a map that already has the column (getOrInsertColumn keeps its
+// statistics, which setValue then adds to, :92).
+bool vgaThroughVision(PointMap& map, Communicator* comm) {
+    dmx_ctx* ctx = context();
+    if (!ctx || !map.isProcessed()) return false;
+    if (map.getAttributeTable().hasColumn("__Internal_Gate") || map.getAttributeTable().hasColumn("Through vision"))
+        return false;
+    const std::string img = save(map);
+    Owned<dmx_chunk, dmx_chunk_free> c;
+    check(dmx_chunk_parse(reinterpret_cast<const uint8_t*>(img.data()), (int64_t)img.size(), &c.p));
+    const QtRegion* parent = RegionAccess::parent(map);
+    const double region[4] = {parent->bottom_left.x, parent->bottom_left.y, parent->top_right.x, parent->top_right.y};
+    Owned<dmx_pointmap, dmx_pointmap_free> pm;
+    Owned<dmx_graph, dmx_graph_free> g;
+    check(dmx_chunk_load(ctx, c.p, region, &pm.p, &g.p));
+    int64_t n = 0, nb = 0, ne = 0, nruns = 0;
+    check(dmx_graph_info(g.p, &n, &nb, &ne, &nruns));
+    std::vector<float> out((size_t)n);
+    {
+        ScopedProgress sp(ctx, comm);
+        const int rc = dmx_vga_thruvision(ctx, g.p, 0, -1, out.data(), nullptr);
+        if (rc == DMX_ERR_UNSUPPORTED) return false;   // a count above the reference's int: its own (wrapping) code
+        check(rc);
+    }
+    // one column, set for every row, not locked, displayed (:92-101)
+    check(dmx_chunk_set_column(c.p, "Through vision", out.data(), nullptr, 0, 1));
+    return load(map, serialize(c.p));
+}
+
 }  // namespace dmxsala

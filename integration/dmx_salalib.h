@@ -1,9 +1,10 @@
 // dmx_salalib.h -- reference-side binding: route salalib's makeGraph and VGA global to libdmx.so.
 //
-// A maintainer adds integration/dmx_salalib.cpp to salalib and calls these at the top of the two
+// A maintainer adds integration/dmx_salalib.cpp to salalib and calls these at the top of the
 // methods they accelerate (INTEGRATION.md shows the two-line hooks):
 //   PointMap::sparkGraph2        salalib/pointdata.cpp:1246-1341
 //   VGAVisualGlobal::run         salalib/vgamodules/vgavisualglobal.cpp:23-216
+//   VGAThroughVision::run        salalib/vgamodules/vgathroughvision.cpp:27-104
 // Each returns true when the engine ran the analysis and `map` now holds exactly what the reference
 // method would have left in it (the point states, nodes, attribute columns and statistics, through
 // the reference's own PointMap::read of the engine's byte-identical PointMap::write image), and false
@@ -20,6 +21,9 @@ namespace dmxsala {
 
 bool sparkGraph2(PointMap& map, Communicator* comm, bool boundarygraph, double maxdist);
 bool vgaVisualGlobal(PointMap& map, Communicator* comm, double radius, bool gates_only, bool simple_version);
+// VGAThroughVision::run (salalib/vgamodules/vgathroughvision.cpp:27-104); false also for a map with the gate
+// column __Internal_Gate (the gate-counting branch, :61-74) or one that already has "Through vision".
+bool vgaThroughVision(PointMap& map, Communicator* comm);
 
 // Test hooks (integration/bind_check.cpp): the PointMap <-> PointMap::write image conversions the two
 // calls are built on.
