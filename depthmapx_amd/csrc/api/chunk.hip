@@ -224,6 +224,29 @@ int dmx_chunk_merges(const dmx_chunk* c, int32_t* cell_pairs, int64_t* n) {
     return DMX_OK;
 }
 
+// The isovist analysis's per-node data a parsed chunk stores (Bin::m_occ_distance, Node::m_occlusion_bins).
+int dmx_chunk_occlusion(const dmx_chunk* c, float* occ_dist, int32_t* occ_counts, int32_t* occ_pixels, int64_t cap,
+                        int64_t* total) {
+    if (!c) return fail(DMX_ERR_ARG, "chunk is NULL");
+    const ParsedChunk& p = c->pc;
+    if (occ_dist && !p.occ_dist.empty()) std::memcpy(occ_dist, p.occ_dist.data(), p.occ_dist.size() * 4);
+    if (occ_counts && !p.occ_counts.empty()) std::memcpy(occ_counts, p.occ_counts.data(), p.occ_counts.size() * 4);
+    if (occ_pixels && cap >= (int64_t)p.occ_pixels.size() && !p.occ_pixels.empty())
+        std::memcpy(occ_pixels, p.occ_pixels.data(), p.occ_pixels.size() * 4);
+    if (total) *total = (int64_t)p.occ_pixels.size();
+    return DMX_OK;
+}
+
+int dmx_chunk_set_occlusion(dmx_chunk* c, const float* occ_dist, const int32_t* occ_counts, const int32_t* occ_pixels) {
+    if (!c || !occ_dist || !occ_counts) return fail(DMX_ERR_ARG, "bad arguments");
+    int64_t total = 0;
+    for (size_t i = 0; i < c->pc.gridconn.size() * 32; i++) total += occ_counts[i] > 0 ? occ_counts[i] : 0;
+    if (total && !occ_pixels) return fail(DMX_ERR_ARG, "occlusion counts without pixels");
+    std::string err;
+    if (chunk_set_occlusion(c->pc, occ_dist, occ_counts, occ_pixels, err)) return fail(DMX_ERR_ARG, err);
+    return DMX_OK;
+}
+
 int dmx_chunk_flags(const dmx_chunk* c, int* processed, int* boundary, int64_t* merges, int64_t* nrows) {
     if (!c) return fail(DMX_ERR_ARG, "chunk is NULL");
     if (processed) *processed = c->pc.processed ? 1 : 0;

@@ -24,6 +24,7 @@
 
 #include "../../include/dmx.h"
 #include "policy.hpp"
+#include "host/bsptree.hpp"
 #include "host/graphfile.hpp"
 #include "host/graphio.hpp"
 #include "host/pointmap.hpp"
@@ -37,6 +38,7 @@
 #include "kernels/vstep.hip"
 #include "kernels/vga_ordered.hip"
 #include "kernels/thruvision.hip"
+#include "kernels/isovist.hip"
 
 using namespace dmx;
 
@@ -205,6 +207,8 @@ struct dmx_ctx {
     double progress_interval = 0.5;
     hipEvent_t ev_poll = nullptr;
     double last_fill_s[2] = {0, 0};   // GPU fill: blockLines, flood fill
+    double last_iso_bsp_s = 0, last_iso_kernel_s = 0;   // isovist: host BSP build, kernels
+    long long last_iso[4] = {0, 0, 0, 0};   // isovist: tree nodes, tree depth, cells re-run for capacity, most blocks
     double sqrt_err = 0.0;            // makeGraph moment square root: measured error bound (mk_sqrt_err)
     long long sqrt_err_nmax = 0;      // ... over 1..sqrt_err_nmax
     long long last_fill_levels = 0;
@@ -683,6 +687,7 @@ int dmx_ctx_last_timing(dmx_ctx* c, double* mk, double* vga) {
 #include "api/vga_global.hip"
 #include "api/vga_other.hip"
 #include "api/thruvision.hip"
+#include "api/isovist.hip"
 #include "api/stepdepth.hip"
 #include "api/chunk.hip"
 #include "api/graphfile.hip"

@@ -309,6 +309,74 @@ int chunk_set_column(ParsedChunk& pc, const std::string& name, const float* valu
     return idx;
 }
 
+int chunk_set_occlusion(ParsedChunk& pc, const float* occ_dist, const int32_t* occ_counts, const int32_t* occ_pixels,
+                        std::string& err) {
+    const size_t C = (size_t)pc.cols * pc.rows;
+    if (pc.point_off.size() != C + 1) { err = "chunk has no point records"; return -1; }
+    const size_t N = pc.gridconn.size();
+    for (size_t i = 0; i < N * 32; i++)
+        if (occ_counts[i] < 0) { err = "negative occlusion count"; return -1; }
+    std::vector<uint8_t> pts;
+    std::vector<uint64_t> off(C + 1, 0);
+    Writer w{pts};
+    size_t k = 0, px = 0;
+    for (size_t i = 0; i < C; i++) {
+        const uint8_t* rec = pc.points_raw.data() + pc.point_off[i];
+        const size_t len = (size_t)(pc.point_off[i + 1] - pc.point_off[i]);
+        off[i] = pts.size();
+        if (len < 34 || !rec[17]) {   // no node: the record as it is
+            pts.insert(pts.end(), rec, rec + len);
+            continue;
+        }
+        if (k >= N) { err = "more node records than nodes"; return -1; }
+        pts.insert(pts.end(), rec, rec + 18);
+        Reader r{rec, len};
+        r.o = 18;
+        for (int b = 0; b < 32 && r.ok; b++) {   // Bin::write: dir, node count, distance, occ distance, runs
+            const size_t b0 = r.o;
+            const uint8_t dir = r.get<uint8_t>();
+            const uint16_t count = r.get<uint16_t>();
+            (void)r.get<float>();
+            pts.insert(pts.end(), rec + b0, rec + b0 + 7);
+            (void)r.get<float>();
+            w.put<float>(occ_dist[k * 32 + b]);
+            const size_t r0 = r.o;
+            if (count) {
+                if (dir & DIR_DIAG) r.o += 6;
+                else {
+                    const uint16_t n = r.get<uint16_t>();
+                    r.o += 6 + (n ? (size_t)(n - 1) * 4 : 0);
+                }
+            }
+            if (r.o > len) { err = "damaged node record"; return -1; }
+            pts.insert(pts.end(), rec + r0, rec + r.o);
+        }
+        for (int b = 0; b < 32 && r.ok; b++) {   // the stored occlusion bins are replaced
+            const uint32_t n = r.get<uint32_t>();
+            r.o += (size_t)n * 4;
+        }
+        if (!r.ok || r.o + 16 != len) { err = "damaged node record"; return -1; }
+        for (int b = 0; b < 32; b++) {   // Node::write: per bin the PixelRef vector
+            const int32_t n = occ_counts[k * 32 + b];
+            w.put<uint32_t>((uint32_t)n);
+            for (int32_t j = 0; j < n; j++, px++) {   // int(PixelRef) -> {short x, short y}
+                w.put<int16_t>((int16_t)(occ_pixels[px] >> 16));
+                w.put<int16_t>((int16_t)(occ_pixels[px] & 0xffff));
+            }
+        }
+        pts.insert(pts.end(), rec + len - 16, rec + len);   // m_location
+        k++;
+    }
+    if (k != N) { err = "node records do not match the nodes"; return -1; }
+    off[C] = pts.size();
+    pc.points_raw.swap(pts);
+    pc.point_off.swap(off);
+    pc.occ_dist.assign(occ_dist, occ_dist + N * 32);
+    pc.occ_counts.assign(occ_counts, occ_counts + N * 32);
+    pc.occ_pixels.assign(occ_pixels, occ_pixels + px);
+    return 0;
+}
+
 int chunk_unmake(ParsedChunk& pc, bool remove_links, std::string& err) {
     std::vector<uint8_t> pts;
     const size_t C = (size_t)pc.cols * pc.rows;
@@ -345,6 +413,9 @@ int chunk_unmake(ParsedChunk& pc, bool remove_links, std::string& err) {
     pc.gridconn.clear();
     pc.bins.clear();
     pc.runs.clear();
+    pc.occ_dist.clear();
+    pc.occ_counts.clear();
+    pc.occ_pixels.clear();
     for (size_t i = 0; i < C; i++) pc.state[i] &= ~CELL_BLOCKED;
     return 0;
 }
@@ -417,6 +488,9 @@ int read_pointmap_chunk(const uint8_t* buf, size_t size, ParsedChunk& pc, std::s
     pc.gridconn.clear();
     pc.bins.clear();
     pc.runs.clear();
+    pc.occ_dist.clear();
+    pc.occ_counts.clear();
+    pc.occ_pixels.clear();
     pc.points_raw.clear();
     pc.point_off.assign((size_t)C + 1, 0);
     pc.merges = 0;
@@ -442,7 +516,7 @@ int read_pointmap_chunk(const uint8_t* buf, size_t size, ParsedChunk& pc, std::s
                     const uint8_t dir = r.get<uint8_t>();
                     const uint16_t count = r.get<uint16_t>();
                     const float dist = r.get<float>();
-                    (void)r.get<float>();
+                    pc.occ_dist.push_back(r.get<float>());   // m_occ_distance
                     int32_t bn[4] = {dir, count, 0, 0};
                     std::memcpy(&bn[2], &dist, 4);
                     if (count) {
@@ -478,8 +552,13 @@ int read_pointmap_chunk(const uint8_t* buf, size_t size, ParsedChunk& pc, std::s
                     pc.bins.insert(pc.bins.end(), bn, bn + 4);
                 }
                 for (int b = 0; b < 32 && r.ok; b++) {
-                    const uint32_t n = r.get<uint32_t>();
-                    r.o += (size_t)n * 4;   // occlusion bins (PixelRef entries)
+                    const uint32_t n = r.get<uint32_t>();   // occlusion bins (PixelRef entries)
+                    if (!r.ok || (size_t)n * 4 > size - std::min(r.o, size)) { r.ok = false; break; }
+                    pc.occ_counts.push_back((int32_t)n);
+                    for (uint32_t i = 0; i < n; i++) {   // PixelRef {short x, short y} as stored -> int(PixelRef)
+                        const int16_t ox = r.get<int16_t>(), oy = r.get<int16_t>();
+                        pc.occ_pixels.push_back(pixref(ox, oy));
+                    }
                 }
             }
             (void)r.get<double>();

@@ -32,6 +32,10 @@ struct ParsedChunk {
     std::vector<uint8_t> gridconn;      // [N]
     std::vector<int32_t> bins;          // [N][32][4] dir, node count, distance bits, runs
     std::vector<int16_t> runs;          // [R][4] as decoded (4-bit shift quirk applied)
+    // the isovist analysis's per-node data (Node::m_occlusion_bins, Bin::m_occ_distance), as stored
+    std::vector<float> occ_dist;        // [N][32]
+    std::vector<int32_t> occ_counts;    // [N][32]
+    std::vector<int32_t> occ_pixels;    // PixelRef ints by node, bin, stored order
     bool processed = false, boundary = false;
     size_t bytes_used = 0;
     // structural pieces for a faithful rewrite (PointMap::read then ::write, pointdata.cpp:1073-1188)
@@ -58,6 +62,11 @@ int write_parsed_chunk(const ParsedChunk& pc, std::vector<uint8_t>& out, std::st
 // AttributeTable::insertOrResetColumn / insertOrResetLockedColumn (attributetable.cpp:303-326) followed
 // by setValue on the rows in `set` (empty: every row); returns the physical column index.
 int chunk_set_column(ParsedChunk& pc, const std::string& name, const float* values, const uint8_t* set, bool locked);
+// Rewrites the node records so that write_parsed_chunk emits these occ distances (Bin::write, ngraph.cpp:447-472)
+// and occlusion bins (Node::write, ngraph.cpp:209-220): occ_dist [N][32], occ_counts [N][32], occ_pixels by
+// node, bin, order (sum of the counts entries).
+int chunk_set_occlusion(ParsedChunk& pc, const float* occ_dist, const int32_t* occ_counts, const int32_t* occ_pixels,
+                        std::string& err);
 // PointMap::unmake(removeLinks) (pointdata.cpp:1343-1374) on the parsed records.
 int chunk_unmake(ParsedChunk& pc, bool remove_links, std::string& err);
 

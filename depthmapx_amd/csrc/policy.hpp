@@ -42,6 +42,24 @@ constexpr int kTvWindow = 64;
 // the largest window the DMX_TV_WINDOW hook accepts (128^2 counters; next to the kernel's static 3 KiB)
 constexpr int kTvWindowMaxBytes = 64 * 1024;
 
+// ---- VGA isovist (isovist.hip)
+// per-lane list capacities of the first launch: the synthetic maps up to 128^2 need at most 14 gaps and 88 blocks
+// (tests/isovist/isovist_check.cpp prints both); a lane's lists take gcap * 20 + bcap * 52 bytes of HBM.  Cells
+// that need more are run again with kIsoRetryFactor times as much.  Hooks: DMX_ISO_GCAP, DMX_ISO_BCAP (tests
+// shrink them to force the second launch).
+constexpr int kIsoGapCap = 32;
+constexpr int kIsoBlockCap = 128;
+constexpr int kIsoRetryFactor = 16;
+constexpr int kIsoCapMax = 1 << 16;   // the largest capacity a hook or the retry may ask for
+// workgroups (of one wave) per CU the persistent kernel is launched with, if the occupancy query allows: 8 is
+// what the kernel's 170 VGPRs admit (2 waves a SIMD).  1000^2, columns only: 33.1 ms with 2, 23.5 ms with 4,
+// 15.6 ms with 8, 15.9 ms with 16 (capped at 8 by occupancy); syn128's 289 tiles show no difference
+// (profiles/isovist_ab.jsonl).  Hook: DMX_ISO_WAVES.
+constexpr int kIsoWavesPerCu = 8;
+// pool entries (8 bytes) per node the first launch reserves for occlusion pixels; a pool found too small is
+// enlarged to what the cursor counted and the launch repeated
+constexpr int kIsoPoolPerNode = 48;
+
 // ---- memory: optional summaries are built only within a share of the free device memory, so a graph
 // that fills the GPU still runs (on the slower exact path that needs no summary)
 // tile rows (tvis / ftvis) and partial-tile masks on narrow grids: a quarter of the free memory

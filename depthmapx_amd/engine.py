@@ -62,7 +62,8 @@ class Context:
         N.check(N.lib().dmx_ctx_set_progress(self.h, self._progress, None, float(interval_s)))
 
     def cancel(self):
-        """Cancel the running (or next) makeGraph / VGA-global / step-depth call (any thread)."""
+        """Cancel the running (or next) makeGraph / VGA-global / through-vision / isovist / step-depth call (any
+        thread)."""
         N.check(N.lib().dmx_ctx_cancel(self.h))
 
     def last_fill(self):
@@ -84,6 +85,15 @@ class Context:
         return dict(seconds=t.value, expanders_popped=p.value, cells_relaxed=r.value,
                     mode=["serial", "batched", "batched-overflow-serial"][int(d[0])], batches=int(d[1]),
                     improved=int(d[2]), ambiguous=int(d[3]))
+
+    def last_isovist(self):
+        """The last Graph.vga_isovist (dmx_ctx_last_isovist): seconds of the host BSP build and of the kernels,
+        the tree's nodes and depth, the cells run again for capacity and the most blocks any cell held."""
+        b, k = ctypes.c_double(), ctypes.c_double()
+        d = np.zeros(4, dtype=np.int64)
+        N.check(N.lib().dmx_ctx_last_isovist(self.h, ctypes.byref(b), ctypes.byref(k), N.ptr(d)))
+        return dict(bsp_seconds=b.value, kernel_seconds=k.value, tree_nodes=int(d[0]), tree_depth=int(d[1]),
+                    reruns=int(d[2]), max_blocks=int(d[3]))
 
     def last_mk_reruns(self):
         """The sources the last makeGraph swept again: (certificate re-runs, capacity re-runs), node indices
@@ -375,6 +385,37 @@ class Graph:
         N.check(N.lib().dmx_vga_thruvision(self.ctx.h, self.h, int(src_begin), int(src_end), N.ptr(out),
                                            N.ptr(cnt)))
         return (out, cnt) if counts else out
+
+    ISOVIST_COLUMNS = ["Isovist Area", "Isovist Compactness", "Isovist Drift Angle", "Isovist Drift Magnitude",
+                       "Isovist Max Radial", "Isovist Min Radial", "Isovist Occlusivity", "Isovist Perimeter"]
+
+    def vga_isovist(self, simple=False, src_begin=0, src_end=-1, occlusion=False, out=None):
+        """VGA -vm isovist (VGAIsovist::run, vgamodules/vgaisovist.cpp:24-90) on the GPU: [N][8] float32, the
+        columns of ISOVIST_COLUMNS (table order).  Rows start at -1 (or at `out`, which is updated in place);
+        only the rows of nodes [src_begin, src_end) are written, of those not the cells the reference skips
+        (context-filled at an odd PixelRef), and with simple=True only column 0.  occlusion=True also returns
+        a dict: occ_dist float32 [N][32], occ_counts int32 [N][32] (rows not written: 0) and occ_pixels int32
+        [total], packed PixelRefs by node, bin and the reference's push order."""
+        n = self.info()["nnodes"]
+        if out is None:
+            out = np.full((n, 8), -1.0, dtype=np.float32)
+        assert out.dtype == np.float32 and out.shape == (n, 8) and out.flags["C_CONTIGUOUS"]
+        lib = N.lib()
+        if not occlusion:
+            N.check(lib.dmx_vga_isovist(self.ctx.h, self.h, int(bool(simple)), int(src_begin), int(src_end), N.ptr(out),
+                                        None, None, None, 0, None))
+            return out
+        dist = np.zeros((n, 32), dtype=np.float32)
+        counts = np.zeros((n, 32), dtype=np.int32)
+        total = ctypes.c_int64()
+        pix = np.zeros(max(64 * n, 1), dtype=np.int32)   # a guess; the call reports the number when it is too small
+        for _ in range(2):
+            N.check(lib.dmx_vga_isovist(self.ctx.h, self.h, int(bool(simple)), int(src_begin), int(src_end), N.ptr(out),
+                                        N.ptr(dist), N.ptr(counts), N.ptr(pix), len(pix), ctypes.byref(total)))
+            if total.value <= len(pix):
+                break
+            pix = np.zeros(total.value, dtype=np.int32)
+        return out, dict(occ_dist=dist, occ_counts=counts, occ_pixels=pix[:total.value])
 
     def metric_step_depth(self, points=None, cells=None):
         """STEPDEPTH -sdt metric (dm_runmethods::runStepDepth, depthmapXcli/runmethods.cpp:735-778):

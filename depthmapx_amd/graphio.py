@@ -97,3 +97,34 @@ def load_chunk(ctx, blob, region, lines=None):
     if lines is not None:
         g.set_drawing(lines)
     return pm, g
+
+
+def chunk_occlusion(blob):
+    """The isovist analysis's per-node data a chunk stores (dmx_chunk_occlusion): occ_dist float32 [N][32],
+    occ_counts int32 [N][32], occ_pixels int32 [total] (packed PixelRefs by node, bin, stored order)."""
+    c = _Chunk(blob)
+    n = read_chunk(blob)["nnodes"]
+    dist = np.zeros((n, 32), dtype=np.float32)
+    counts = np.zeros((n, 32), dtype=np.int32)
+    total = ctypes.c_int64()
+    N.check(N.lib().dmx_chunk_occlusion(c.h, N.ptr(dist), N.ptr(counts), None, 0, ctypes.byref(total)))
+    pix = np.zeros(max(total.value, 1), dtype=np.int32)
+    N.check(N.lib().dmx_chunk_occlusion(c.h, None, None, N.ptr(pix), total.value, ctypes.byref(total)))
+    return dict(occ_dist=dist, occ_counts=counts, occ_pixels=pix[:total.value])
+
+
+def set_chunk_occlusion(blob, occ_dist, occ_counts, occ_pixels):
+    """The chunk's bytes with this per-node isovist data in its node records (dmx_chunk_set_occlusion, then
+    dmx_chunk_serialize); occ_dist None: the chunk serialised as it is."""
+    c = _Chunk(blob)
+    if occ_dist is not None:
+        d = np.ascontiguousarray(occ_dist, dtype=np.float32)
+        k = np.ascontiguousarray(occ_counts, dtype=np.int32)
+        p = np.ascontiguousarray(occ_pixels, dtype=np.int32)
+        assert k.sum() == len(p)
+        N.check(N.lib().dmx_chunk_set_occlusion(c.h, N.ptr(d), N.ptr(k), N.ptr(p) if len(p) else None))
+    size = ctypes.c_int64()
+    N.check(N.lib().dmx_chunk_serialize(c.h, None, 0, ctypes.byref(size)))
+    buf = np.zeros(size.value, dtype=np.uint8)
+    N.check(N.lib().dmx_chunk_serialize(c.h, N.ptr(buf), size.value, ctypes.byref(size)))
+    return buf.tobytes()

@@ -67,7 +67,7 @@ typedef int32_t (*dmx_progress_fn)(void* user, int32_t phase, int64_t done, int6
 int dmx_ctx_set_progress(dmx_ctx* ctx, dmx_progress_fn fn, void* user, double interval_s);
 /* Request cancellation of the operation running on ctx (callable from any thread).  The request is
  * consumed by the operation that observes it; one made while no operation runs cancels the next
- * makegraph, VGA-global, through-vision or step-depth (metric, angular, visual) call at its first poll -- before that
+ * makegraph, VGA-global, through-vision, isovist or step-depth (metric, angular, visual) call at its first poll -- before that
  * call writes any output.  VGA local / metric / angular do not poll (a pending request waits). */
 int dmx_ctx_cancel(dmx_ctx* ctx);
 /* Wall time of the kernels of the last makegraph / vga call, measured with HIP events on the
@@ -246,6 +246,34 @@ int dmx_vga_local(dmx_ctx* ctx, dmx_graph* g, int gates_only, int64_t src_begin,
  * cancel as in dmx_vga_global. */
 int dmx_vga_thruvision(dmx_ctx* ctx, dmx_graph* g, int64_t src_begin, int64_t src_end,
                        float* out /* host [N] */, int64_t* counts /* host [N], optional */);
+/* ---- VGA isovist analysis (GPU) -------------------------------------------------------------- */
+/* MetaGraph::analyseGraph(OUTPUT_ISOVIST) -> VGAIsovist().run (salalib/mgraph.cpp:346-348,
+ * vgamodules/vgaisovist.cpp:24-129; what depthmapXcli -m VGA runs without -vm): a BSP tree of the drawing lines
+ * is built on the host, and for every node in [src_begin, src_end) (src_end < 0: all) the isovist polygon of the
+ * cell centre is made by walking the tree front to back (Isovist::makeit, salalib/isovist.cpp).  The lines are
+ * those the graph's point map was created with, or those given to dmx_graph_set_drawing (a chunk-loaded map);
+ * DMX_ERR_STATE if there are none.  The graph must hold every node (DMX_ERR_STATE otherwise).
+ *   out         host [N][8], node order, columns in table order: Isovist Area, Compactness, Drift Angle, Drift
+ *               Magnitude, Max Radial, Min Radial, Occlusivity, Perimeter.  Only rows of the range are written, and
+ *               of those not the cells the reference skips (context-filled at an odd PixelRef, vgaisovist.cpp:50-52:
+ *               their rows keep what they held, -1 in a fresh table).  simple_version: only column 0 is written.
+ *   occ_dist    optional, host [N][32]: Bin::m_occ_distance of every bin (rows as for out)
+ *   occ_counts  optional, host [N][32]: sizes of Node::m_occlusion_bins (rows as for out)
+ *   occ_pixels  optional, host [occ_cap]: the PixelRefs of the occlusion bins of the rows written, packed as the
+ *               reference packs them ((x << 16) + (y & 0xffff)), by node, then bin, then the reference's push order.
+ *               *occ_total (optional) receives their number; occ_pixels NULL or occ_cap < *occ_total: only
+ *               *occ_total is set.
+ * Results depend on the platform's acos / sin / cos in the last bit of FP64, which the rounding to float hides
+ * except where the reference itself is unstable.  Per-cell lists have fixed capacities
+ * (policy.hpp); a cell that exceeds one is run again with larger lists, DMX_ERR_CAPACITY only after that.
+ * Progress and cancel as in dmx_vga_thruvision (phase DMX_PHASE_VGA; the unit is a tile of 8 x 8 cells). */
+int dmx_vga_isovist(dmx_ctx* ctx, dmx_graph* g, int simple_version, int64_t src_begin, int64_t src_end,
+                    float* out /* host [N][8] */, float* occ_dist /* host [N][32], optional */,
+                    int32_t* occ_counts /* host [N][32], optional */, int32_t* occ_pixels, int64_t occ_cap,
+                    int64_t* occ_total);
+/* The last dmx_vga_isovist: seconds of the host BSP build and of the kernels (either may be NULL), and out4 =
+ * tree nodes, tree depth, cells run again for capacity, the most blocks a cell held. */
+int dmx_ctx_last_isovist(dmx_ctx* ctx, double* bsp_s, double* kernel_s, int64_t* out4);
 /* Multi-GPU share of the VGA preparation (no reference counterpart: the reference prepares nothing;
  * this splits our own O(runs) pre-passes).  Every rank holds the whole graph; the per-node scatters
  * (in-set hash sums, tile-visibility rows) then run over nodes [node_begin, node_end)
@@ -359,6 +387,16 @@ int dmx_chunk_flags(const dmx_chunk* c, int* processed, int* boundary, int64_t* 
 int dmx_chunk_set_column(dmx_chunk* c, const char* name, const float* values, const uint8_t* setmask, int locked,
                          int make_displayed);
 int dmx_chunk_set_displayed(dmx_chunk* c, int physical_column);
+/* The isovist analysis's per-node data as the chunk stores it (PointMap::read reads it back, the agent engine
+ * consumes it): occ_dist [N][32] Bin::m_occ_distance, occ_counts [N][32] the sizes of Node::m_occlusion_bins,
+ * occ_pixels their PixelRefs packed (x << 16) + (y & 0xffff), by node, bin, stored order; any may be NULL, and
+ * occ_pixels is filled only when cap holds them all.  *total: the number of PixelRefs. */
+int dmx_chunk_occlusion(const dmx_chunk* c, float* occ_dist, int32_t* occ_counts, int32_t* occ_pixels, int64_t cap,
+                        int64_t* total);
+/* Rewrites the node records so that dmx_chunk_serialize emits this data as Node::write and Bin::write do
+ * (ngraph.cpp:209-220, :447-472).  A chunk it was never called on serialises byte for byte as before. */
+int dmx_chunk_set_occlusion(dmx_chunk* c, const float* occ_dist, const int32_t* occ_counts, const int32_t* occ_pixels);
+
 int dmx_chunk_set_name(dmx_chunk* c, const char* name);
 /* PointMap::setCurSel(r, add) of the STEPDEPTH selection (runmethods.cpp:745-753): Point::SELECTED on the
  * filled cells among `cells` (x-major indices); MetaGraph::write then saves it. */

@@ -269,4 +269,79 @@ bool vgaThroughVision(PointMap& map, Communicator* comm) {
     return load(map, serialize(c.p));
 }
 
+// VGAIsovist::run (vgaisovist.cpp:24-90): the eight columns, and per node the occlusion bins and occ distances
+// (Node::m_occlusion_bins, Bin::m_occ_distance), which travel in the node records of the image.  A map that
+// already has "Isovist Area" keeps the reference path (getOrInsertColumn keeps the column's statistics, which
+// setValue then adds to).
+bool vgaIsovist(PointMap& map, Communicator* comm, bool simple_version) {
+    dmx_ctx* ctx = context();
+    if (!ctx || !map.isProcessed()) return false;
+    if (map.getAttributeTable().hasColumn("Isovist Area")) return false;
+    const std::vector<double> lines = drawing_lines(map);
+    if (lines.empty()) return false;
+    const std::string img = save(map);
+    Owned<dmx_chunk, dmx_chunk_free> c;
+    check(dmx_chunk_parse(reinterpret_cast<const uint8_t*>(img.data()), (int64_t)img.size(), &c.p));
+    const QtRegion* parent = RegionAccess::parent(map);
+    const double region[4] = {parent->bottom_left.x, parent->bottom_left.y, parent->top_right.x, parent->top_right.y};
+    Owned<dmx_pointmap, dmx_pointmap_free> pm;
+    Owned<dmx_graph, dmx_graph_free> g;
+    check(dmx_chunk_load(ctx, c.p, region, &pm.p, &g.p));
+    check(dmx_graph_set_drawing(g.p, lines.data(), (int64_t)lines.size() / 4));
+    int64_t n = 0, nb = 0, ne = 0, nruns = 0;
+    check(dmx_graph_info(g.p, &n, &nb, &ne, &nruns));
+    // what the skipped cells keep: the occ data the map holds now
+    std::vector<float> out((size_t)n * 8, -1.0f), occ_dist((size_t)n * 32);
+    std::vector<int32_t> occ_counts((size_t)n * 32), old_pix, new_pix;
+    int64_t old_total = 0, total = 0;
+    check(dmx_chunk_occlusion(c.p, occ_dist.data(), occ_counts.data(), nullptr, 0, &old_total));
+    old_pix.resize((size_t)std::max<int64_t>(old_total, 1));
+    check(dmx_chunk_occlusion(c.p, nullptr, nullptr, old_pix.data(), old_total, &old_total));
+    const std::vector<int32_t> old_counts = occ_counts;
+    // the rows the reference writes: every filled point but the context-filled ones at odd PixelRefs (:48-52)
+    std::vector<uint8_t> set;
+    for (size_t x = 0; x < map.getCols(); x++)
+        for (size_t y = 0; y < map.getRows(); y++) {
+            const PixelRef curs((short)x, (short)y);
+            if (map.getPoint(curs).filled()) set.push_back(map.getPoint(curs).contextfilled() && !curs.iseven() ? 0 : 1);
+        }
+    if ((int64_t)set.size() != n) return false;
+    {
+        ScopedProgress sp(ctx, comm);
+        check(dmx_vga_isovist(ctx, g.p, simple_version ? 1 : 0, 0, -1, out.data(), occ_dist.data(), occ_counts.data(),
+                              nullptr, 0, &total));
+        new_pix.resize((size_t)std::max<int64_t>(total, 1));
+        check(dmx_vga_isovist(ctx, g.p, simple_version ? 1 : 0, 0, -1, out.data(), occ_dist.data(), occ_counts.data(),
+                              new_pix.data(), total, &total));
+    }
+    // pixels by node: the new lists of the rows written, the old ones of the skipped rows
+    std::vector<int32_t> pix;
+    size_t oo = 0, no = 0;
+    for (int64_t k = 0; k < n; k++) {
+        size_t oc = 0, nc = 0;
+        for (int b = 0; b < 32; b++) {
+            oc += (size_t)old_counts[(size_t)k * 32 + b];
+            if (set[k]) nc += (size_t)occ_counts[(size_t)k * 32 + b];
+        }
+        if (set[k]) pix.insert(pix.end(), new_pix.begin() + no, new_pix.begin() + no + nc);
+        else pix.insert(pix.end(), old_pix.begin() + oo, old_pix.begin() + oo + oc);
+        oo += oc;
+        no += nc;
+    }
+    // the columns in the order setData inserts them (isovist.cpp:308-332); none locked, the displayed attribute stays
+    static const struct { const char* name; int k; } cols[8] = {
+        {"Isovist Area", 0}, {"Isovist Compactness", 1}, {"Isovist Drift Angle", 2}, {"Isovist Drift Magnitude", 3},
+        {"Isovist Min Radial", 5}, {"Isovist Max Radial", 4}, {"Isovist Occlusivity", 6}, {"Isovist Perimeter", 7}};
+    std::vector<float> v((size_t)n);
+    for (const auto& col : cols) {
+        if (simple_version && col.k != 0) continue;
+        for (int64_t i = 0; i < n; i++) v[i] = out[(size_t)i * 8 + col.k];
+        check(dmx_chunk_set_column(c.p, col.name, v.data(), set.data(), 0, 0));
+    }
+    check(dmx_chunk_set_occlusion(c.p, occ_dist.data(), occ_counts.data(), pix.empty() ? nullptr : pix.data()));
+    if (!load(map, serialize(c.p))) return false;
+    map.m_hasIsovistAnalysis = true;
+    return true;
+}
+
 }  // namespace dmxsala

@@ -5,6 +5,7 @@
 //   PointMap::sparkGraph2        salalib/pointdata.cpp:1246-1341
 //   VGAVisualGlobal::run         salalib/vgamodules/vgavisualglobal.cpp:23-216
 //   VGAThroughVision::run        salalib/vgamodules/vgathroughvision.cpp:27-104
+//   VGAIsovist::run              salalib/vgamodules/vgaisovist.cpp:24-90
 // Each returns true when the engine ran the analysis and `map` now holds exactly what the reference
 // method would have left in it (the point states, nodes, attribute columns and statistics, through
 // the reference's own PointMap::read of the engine's byte-identical PointMap::write image), and false
@@ -24,6 +25,10 @@ bool vgaVisualGlobal(PointMap& map, Communicator* comm, double radius, bool gate
 // VGAThroughVision::run (salalib/vgamodules/vgathroughvision.cpp:27-104); false also for a map with the gate
 // column __Internal_Gate (the gate-counting branch, :61-74) or one that already has "Through vision".
 bool vgaThroughVision(PointMap& map, Communicator* comm);
+// VGAIsovist::run (salalib/vgamodules/vgaisovist.cpp:24-90): the eight isovist columns, the nodes' occlusion bins
+// and occ distances, m_hasIsovistAnalysis; false also for a map without drawing lines or one that already has
+// "Isovist Area".  Values agree with the reference within 1e-6 relative (the platform's acos / sin / cos).
+bool vgaIsovist(PointMap& map, Communicator* comm, bool simple_version);
 
 // Test hooks (integration/bind_check.cpp): the PointMap <-> PointMap::write image conversions the two
 // calls are built on.
