@@ -199,6 +199,8 @@ int dmx_graph_set_merges(dmx_graph* g, const int32_t* cell_pairs, int64_t n) {
     g->pm->host->set_merge(std::move(per_cell));
     g->merges = std::move(uniq);
     g->merges_ready = false;
+    // the asymmetric mode's preparation was made (or refused) for the previous links: its reference graph has none
+    asym_invalidate(g);
     if (g->merges.empty()) {   // prepare_merges returns early on no links: drop the previous links' device state
         g->nmamb = 0;
         g->d_mamb.reset();

@@ -866,6 +866,34 @@ static int vga_tile_impl(dmx_ctx* ctx, dmx_graph* g, double radius, int gates_on
 // nodes outside A is in both graphs and in both directions, so the search runs bottom-up on R with the frontier
 // limited to cells outside A, and the A cells of each frontier push the graph's own runs top-down.  Needs the
 // drawing (dmx_graph_set_drawing), the whole graph, no merge links, R on the same grid and |A| <= N/4.
+// The preparation is kept on the graph; a new drawing or a change of the links (asym_invalidate) drops it.
+static void asym_invalidate(dmx_graph* g) {
+    g->asym_state = 0;
+    g->asym_why.clear();
+    g->nasym = 0;
+    g->aref.reset();
+    g->aref_pm.reset();
+    g->asym_tiles.reset();
+}
+
+// The context's makeGraph figures (dmx_ctx_last_timing, the mk_* counters of dmx_ctx_last_stats,
+// dmx_ctx_last_mk_reruns) belong to the caller's last makeGraph: put back after a makeGraph run inside another call.
+static const int kMkStatSlots[6] = {0, 1, 2, 32, 33, 34};   // makegraph_impl's slots of last_stats
+struct MkFiguresKeeper {
+    dmx_ctx* ctx;
+    double mk_s;
+    long long stats[6];
+    std::vector<int64_t> reruns;
+    explicit MkFiguresKeeper(dmx_ctx* c) : ctx(c), mk_s(c->last_mk_s), reruns(c->last_mk_reruns) {
+        for (int i = 0; i < 6; i++) stats[i] = c->last_stats[kMkStatSlots[i]];
+    }
+    ~MkFiguresKeeper() {
+        ctx->last_mk_s = mk_s;
+        for (int i = 0; i < 6; i++) ctx->last_stats[kMkStatSlots[i]] = stats[i];
+        ctx->last_mk_reruns = std::move(reruns);
+    }
+};
+
 static int prepare_asym(dmx_ctx* ctx, dmx_graph* g) {
     if (g->asym_state) return g->asym_state > 0 ? DMX_OK : DMX_ERR_UNSUPPORTED;
     g->asym_state = -1;
@@ -885,11 +913,14 @@ static int prepare_asym(dmx_ctx* ctx, dmx_graph* g) {
     hr.restore_fill(h.state().data());
     pm->version++;
     const double t0 = now_s();
-    // (makeGraph's timing and counters are the reference graph's from here on)
     dmx_graph* r = nullptr;
-    if (int rc = makegraph_impl(ctx, pm.get(), -1.0, 0, 0, -1, nullptr, nullptr, &r)) {
-        g->asym_why = "makeGraph of the reference failed";
-        return rc;
+    {
+        // (the context keeps the figures of the caller's own makeGraph, not the reference graph's)
+        MkFiguresKeeper keep(ctx);
+        if (int rc = makegraph_impl(ctx, pm.get(), -1.0, 0, 0, -1, nullptr, nullptr, &r)) {
+            g->asym_why = "makeGraph of the reference failed";
+            return rc;
+        }
     }
     std::unique_ptr<dmx_graph> R(r);
     if (R->nnodes != g->nnodes) { g->asym_why = "the reference has other nodes"; return DMX_ERR_UNSUPPORTED; }
@@ -933,10 +964,7 @@ int dmx_graph_set_drawing(dmx_graph* g, const double* lines, int64_t nlines) {
     if (!g || nlines < 0 || (nlines > 0 && !lines)) return fail(DMX_ERR_ARG, "bad arguments");
     g->drawing.assign(lines, lines + 4 * nlines);
     g->has_drawing = true;
-    g->asym_state = 0;
-    g->aref.reset();
-    g->aref_pm.reset();
-    g->asym_tiles.reset();
+    asym_invalidate(g);
     return DMX_OK;
 }
 

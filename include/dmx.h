@@ -368,7 +368,10 @@ int dmx_graph_set_merges(dmx_graph* g, const int32_t* cell_pairs, int64_t n);
  * drawing, VGA global makes the map's graph again as a symmetric reference and runs the tile search on it, the
  * nodes whose runs differ pushing their own runs (exact; DESIGN.md section 2, asymmetric mode); without it, such
  * a graph takes the top-down search.  Replaces nothing in the reference: its VGA walks the re-read runs as they
- * are (vgavisualglobal.cpp:96-128), which this reproduces. */
+ * are (vgavisualglobal.cpp:96-128), which this reproduces.  The reference graph is made by the first VGA global
+ * call and kept on the graph; a new drawing or dmx_graph_set_merges drops it (a graph with merge links does not run
+ * in this mode, one cleared of them does again).  Making it leaves the context's makeGraph figures
+ * (dmx_ctx_last_timing, the makeGraph counters of dmx_ctx_last_stats, dmx_ctx_last_mk_reruns) as they were. */
 int dmx_graph_set_drawing(dmx_graph* g, const double* lines, int64_t nlines);
 /* The same links on a point map: written into its PointMap chunk (Point::write, point.cpp:51-73) and
  * followed by the graphs made from it (dmx_makegraph, dmx_graph_assemble_device, dmx_graph_from_runs). */

@@ -27,6 +27,25 @@ def make_lines(W, n, seed=1, lmin=0.02, lmax=0.10):
     return lines
 
 
+def make_room_map(W, room, nocc, seed):
+    """A W x W region with a walled room of side `room` near the middle and `nocc` occluders in it: the grid is
+    the whole region's while the filled cells (and the cost of a CPU graph) are the room's.  Returns (region,
+    lines [n][4], seed point inside the room)."""
+    rng = np.random.default_rng(seed)
+    x0 = y0 = W / 2 - room / 2
+    x1 = y1 = x0 + room
+    walls = [[0, 0, W, 0], [W, 0, W, W], [W, W, 0, W], [0, W, 0, 0],
+             [x0, y0, x1, y0], [x1, y0, x1, y1], [x1, y1, x0, y1], [x0, y1, x0, y0]]
+    c = rng.uniform(x0 + 2, x1 - 2, size=(nocc, 2))
+    ang = rng.uniform(0, np.pi, size=nocc)
+    ln = rng.uniform(1.0, room / 6, size=nocc)
+    d = np.stack([np.cos(ang), np.sin(ang)], 1) * (ln / 2)[:, None]
+    lines = np.concatenate([np.array(walls, dtype=np.float64), np.concatenate([c - d, c + d], 1)])
+    region = [0.0, 0.0, float(W), float(W)]
+    seed_pt = (x0 + 1.3, y0 + 1.3)
+    return region, lines, seed_pt
+
+
 def write_csv(path, lines):
     with open(path, "w") as f:
         f.write("x1,y1,x2,y2\n")

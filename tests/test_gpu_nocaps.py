@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import depthmapx_amd as dmx
+from golden.gen_synthetic import make_room_map as _room_map
 from golden_io import case_input_lines, load_case
 
 pytestmark = pytest.mark.gpu
@@ -25,23 +26,6 @@ def _map(meta):
     for f in meta["fills"]:
         assert pm.make_points(*f)
     return pm
-
-
-def _room_map(W, room, nocc, seed):
-    """A W x W region with a walled room of side `room` near the middle and `nocc` occluders in it."""
-    rng = np.random.default_rng(seed)
-    x0 = y0 = W / 2 - room / 2
-    x1 = y1 = x0 + room
-    walls = [[0, 0, W, 0], [W, 0, W, W], [W, W, 0, W], [0, W, 0, 0],
-             [x0, y0, x1, y0], [x1, y0, x1, y1], [x1, y1, x0, y1], [x0, y1, x0, y0]]
-    c = rng.uniform(x0 + 2, x1 - 2, size=(nocc, 2))
-    ang = rng.uniform(0, np.pi, size=nocc)
-    ln = rng.uniform(1.0, room / 6, size=nocc)
-    d = np.stack([np.cos(ang), np.sin(ang)], 1) * (ln / 2)[:, None]
-    lines = np.concatenate([np.array(walls, dtype=np.float64), np.concatenate([c - d, c + d], 1)])
-    region = [0.0, 0.0, float(W), float(W)]
-    seed_pt = (x0 + 1.3, y0 + 1.3)
-    return region, lines, seed_pt
 
 
 @pytest.mark.parametrize("name", ["kat", "syn32", "syn64", "gallery"])
