@@ -83,6 +83,13 @@ static int makegraph_impl(dmx_ctx* ctx, dmx_pointmap* pm, double maxdist, int bo
     g->node_end = node_end;
     inherit_merges(g.get());
     const int D = std::max(h.cols(), h.rows());
+    // Inexact world coordinates: the depths at which whichbin would take some diagonal cell
+    // of this grid out of the diagonal bin, which the kernel gives every diagonal cell.  Reported, not acted on.
+    const int diag_inexact = diag_offbin_depths(h.cols(), h.rows(), h.bottom_left().x, h.bottom_left().y, h.spacing());
+    if (diag_inexact)
+        VLOG("makegraph: inexact world coordinates: at %d of %d depths a diagonal cell's FP64 ratio falls below 1 - 1e-12; "
+             "the reference bins such a cell next to the diagonal bin, this graph keeps it there\n", diag_inexact,
+             std::min(h.cols(), h.rows()) - 1);
     HIPCHK(g->node_run_start.alloc(std::max<int64_t>(n, 1)));
     HIPCHK(g->node_nruns.alloc(std::max<int64_t>(n, 1)));
     HIPCHK(g->bin_nruns.alloc(std::max<int64_t>(n, 1) * 32));
@@ -349,6 +356,7 @@ static int makegraph_impl(dmx_ctx* ctx, dmx_pointmap* pm, double maxdist, int bo
         ctx->last_stats[32] = (long long)st[2];   // sieve depth steps
         ctx->last_stats[33] = (long long)st[3];   // 64-candidate chunks
         ctx->last_stats[34] = (long long)reruns;
+        ctx->last_stats[47] = diag_inexact;
         ctx->last_mk_reruns = std::move(mk_reruns);
         ctx->last_mk_s = mk_total_s + kernel_s;   // every pass counted (sample, overflow re-runs)
         g->nruns = (int64_t)used;

@@ -878,18 +878,18 @@ static void asym_invalidate(dmx_graph* g) {
 
 // The context's makeGraph figures (dmx_ctx_last_timing, the mk_* counters of dmx_ctx_last_stats,
 // dmx_ctx_last_mk_reruns) belong to the caller's last makeGraph: put back after a makeGraph run inside another call.
-static const int kMkStatSlots[6] = {0, 1, 2, 32, 33, 34};   // makegraph_impl's slots of last_stats
+static const int kMkStatSlots[7] = {0, 1, 2, 32, 33, 34, 47};   // makegraph_impl's slots of last_stats
 struct MkFiguresKeeper {
     dmx_ctx* ctx;
     double mk_s;
-    long long stats[6];
+    long long stats[7];
     std::vector<int64_t> reruns;
     explicit MkFiguresKeeper(dmx_ctx* c) : ctx(c), mk_s(c->last_mk_s), reruns(c->last_mk_reruns) {
-        for (int i = 0; i < 6; i++) stats[i] = c->last_stats[kMkStatSlots[i]];
+        for (int i = 0; i < 7; i++) stats[i] = c->last_stats[kMkStatSlots[i]];
     }
     ~MkFiguresKeeper() {
         ctx->last_mk_s = mk_s;
-        for (int i = 0; i < 6; i++) ctx->last_stats[kMkStatSlots[i]] = stats[i];
+        for (int i = 0; i < 7; i++) ctx->last_stats[kMkStatSlots[i]] = stats[i];
         ctx->last_mk_reruns = std::move(reruns);
     }
 };

@@ -846,9 +846,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
                         int bin = -1;
                         double this_dist = 0.0;
                         // whichbin(depixelate(c) - centre) (pointdata.h:432-520) decided on the exact ratio
-                        // ind/depth: 0 and 1 are the axis / diagonal; tan15 and tan30 are irrational, so a float
-                        // test with a 1e-6 margin decides every cell the reference's FP64 ratio (error ~1e-15)
-                        // decides; cells inside the margin take the FP64 path
+                        // ind/depth: 0 is the axis (gy is exactly 0 there); tan15 and tan30 are irrational, so a
+                        // float test with a 1e-6 margin decides every cell the reference's FP64 ratio decides (its
+                        // error is a few ulps of the coordinates over the cell's distance: ~1e-15 with unit
+                        // coordinates, below 1e-8 on an OS-grid origin); cells inside the margin take the FP64 path.
+                        // ind == depth takes the diagonal class without asking: the reference's ratio there is
+                        // exactly 1 only where bottom_left + spacing * index is exact, and on other grids it moves
+                        // some diagonal cells to class 3 of this octant or its partner -- a known divergence
+                        // ("Inexact world coordinates"; the host counts the depths at which it
+                        // can happen, span.hpp diag_offbin_depths), so the diagonal check below compares the forced
+                        // bin with the octant's table and can only catch a broken table
                         {
                             const float fd = (float)depth, fi = (float)ind, mg = 1e-6f * fd;
                             const float e15 = fi - 0.267949192f * fd, e30 = fi - 0.577350269f * fd;

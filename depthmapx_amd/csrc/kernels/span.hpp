@@ -88,7 +88,8 @@ DMX_SPAN_HD inline int obin(unsigned obinp, int k) { return (int)((obinp >> (6 *
 
 // The bin of visible cell (depth, ind): the makeGraph chunk loop's decision, verbatim -- the exact ratio
 // ind/depth decides axis and diagonal; a float test with a 1e-6 margin decides the tan 15 / tan 30 classes;
-// cells inside the margin take the FP64 whichbin of depixelate(cell) - centre.
+// cells inside the margin take the FP64 whichbin of depixelate(cell) - centre.  (ind == depth is the diagonal class
+// whatever the coordinates: see diag_offbin_depths below for the grids on which the reference disagrees.)
 DMX_SPAN_HD inline int cell_bin(const SpanOct& o, int depth, int ind) {
     const float fd = (float)depth, fi = (float)ind, mg = 1e-6f * fd;
     const float e15 = fi - 0.267949192f * fd, e30 = fi - 0.577350269f * fd;
@@ -104,6 +105,35 @@ DMX_SPAN_HD inline int cell_bin(const SpanOct& o, int depth, int ind) {
     }
     return obin(o.obinp, k);
 }
+// The number of depths d at which some diagonal cell (x +- d, y +- d) of some source (x, y) of the grid takes
+// another bin from whichbin than the diagonal bin cell_bin gives every diagonal cell (0: none does).
+// depixelate rounds bottom_left + spacing * index at every cell, so gx = px(x + d) - px(x) and gy = py(y + d) -
+// py(y) need not be one value per d; whichbin calls the cell diagonal when min(|gx|, |gy|) / max(|gx|, |gy|) >=
+// 1 - 1e-12.  A cell's column and row are independent, and IEEE division is monotone, so per d the smallest
+// ratio any cell reaches is min(gy) / max(gx) or min(gx) / max(gy): O((cols + rows) * depths) subtractions, on
+// the host, exact.  (The offsets towards -d are the negated offsets of the cell d before.)
+inline int diag_offbin_depths(int cols, int rows, double blx, double bly, double sp) {
+    int nd = 0;
+    const int D = cols < rows ? cols : rows;
+    for (int d = 1; d < D; d++) {
+        double xl = INFINITY, xh = 0.0, yl = INFINITY, yh = 0.0;
+        for (int x = 0; x + d < cols; x++) {
+            const double g = (blx + sp * 1.0 * (double)(x + d)) - (blx + sp * 1.0 * (double)x);
+            xl = g < xl ? g : xl;
+            xh = g > xh ? g : xh;
+        }
+        for (int y = 0; y + d < rows; y++) {
+            const double g = (bly + sp * 1.0 * (double)(y + d)) - (bly + sp * 1.0 * (double)y);
+            yl = g < yl ? g : yl;
+            yh = g > yh ? g : yh;
+        }
+        // (the larger of the two is the divisor; with yl <= xh the first pair is one whichbin can meet)
+        const double r1 = yl <= xh ? yl / xh : 1.0, r2 = xl <= yh ? xl / yh : 1.0;
+        if ((r1 < r2 ? r1 : r2) < 1.0 - 1e-12) nd++;
+    }
+    return nd;
+}
+
 // its ratio class (the bins of an octant are distinct)
 DMX_SPAN_HD inline int cell_class(const SpanOct& o, int depth, int ind) {
     const int b = cell_bin(o, depth, ind);

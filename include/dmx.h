@@ -89,7 +89,8 @@ int dmx_ctx_last_timing(dmx_ctx* ctx, double* makegraph_s, double* vga_s);
  * 6 row summaries, 7 asymmetric mode), [41] bytes of tile-visibility rows held, [42] bytes of the scan order
  * held, [43] asymmetric mode: nodes whose runs differ from the reference graph (dmx_graph_set_drawing), [44] lines
  * the last through-vision call walked, [45] its pixel steps, [46] its accumulation variant (0 global atomics,
- * else the side of the LDS window).  n <= 48. */
+ * else the side of the LDS window), [47] makeGraph: the depths at which the map's inexact world coordinates take
+ * some diagonal cell out of the diagonal bin in the reference (0: none; see dmx_makegraph).  n <= 48. */
 int dmx_ctx_last_stats(dmx_ctx* ctx, int64_t* out, int n);
 
 /* The sources the last makeGraph swept a second time (graph node indices, in the order the passes listed
@@ -147,7 +148,18 @@ int dmx_pointmap_cell_lines(dmx_pointmap* pm, int32_t* counts, double* pieces, i
 /* ---- makeGraph (GPU) ---------------------------------------------------------------------- */
 /* MetaGraph::makeGraph(comm, boundary, maxdist) -> PointMap::sparkGraph2 (salalib/mgraph.cpp:264-284,
  * pointdata.cpp:1246-1341).  Builds nodes [node_begin, node_end) of the filled cells in x-major
- * order (node_end < 0: all) -- a sub-range is one rank's shard.  maxdist = -1: unrestricted. */
+ * order (node_end < 0: all) -- a sub-range is one rank's shard.  maxdist = -1: unrestricted.
+ * Known divergence, inexact world coordinates: the reference bins a visible cell by
+ * whichbin(depixelate(cell) - centre) (pointdata.cpp:1466, pointdata.h:432-520), and depixelate rounds
+ * bottom_left + spacing * index at every cell.  On grids where those sums are not exact (an OS-grid origin with a
+ * 0.7 m spacing, say; not spacings 2.0 or 0.5 there, and no grid with unit coordinates) a diagonal cell's
+ * |gy| / |gx| can fall below 1 - 1e-12, and the reference puts that cell into the sector bin next to the diagonal
+ * bin.  This engine gives every diagonal cell the diagonal bin: on such a map every node's visible cells and its
+ * three attributes are the reference's, while bin records, run lists and the PointMap chunk's bytes differ at those
+ * cells (a diagonal bin is stored as one run from its first to its last cell, Bin::make, ngraph.cpp:243-258: where a
+ * moved cell was an end of that run beyond a blocked stretch, the reference's run is shorter, and VGA, which walks
+ * runs, then sees fewer cells through it).  The call does not fail; dmx_ctx_last_stats [47] is then non-zero, the same on every rank
+ * (it depends on the grid alone), and DMX_VERBOSE prints a line. */
 int dmx_makegraph(dmx_ctx* ctx, dmx_pointmap* pm, double maxdist, int boundary, int64_t node_begin,
                   int64_t node_end, dmx_graph** out);
 /* Shard bounds for `world` ranks (no reference counterpart: the reference builds the graph on one

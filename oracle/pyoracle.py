@@ -248,6 +248,19 @@ class OracleMap:
         L.dmxo_release_range(self.h, int(node_begin), int(node_end))
         return dict(attrs=attrs, bins=bins, runs=runs[:R], gridconn=gc)
 
+    def graph_range(self, node_begin, node_end):
+        """graph()'s arrays for the nodes [node_begin, node_end) alone, as they are (nothing is computed or freed):
+        after make_graph_sample on a map too large for graph().  gridconn is only set by make_graph[_range]."""
+        L = lib()
+        n = node_end - node_begin
+        R = L.dmxo_num_runs_range(self.h, int(node_begin), int(node_end))
+        attrs = np.zeros((n, 3), dtype=np.float32)
+        bins = np.zeros((n, 32, 4), dtype=np.int32)
+        runs = np.zeros((max(R, 1), 4), dtype=np.int16)
+        gc = np.zeros(n, dtype=np.uint8)
+        L.dmxo_get_graph_range(self.h, int(node_begin), int(node_end), _p(attrs), _p(bins), _p(runs), _p(gc))
+        return dict(attrs=attrs, bins=bins, runs=runs[:R], gridconn=gc)
+
     def make_graph_sample(self, nodes, maxdist=-1.0, threads=1):
         """sparkPixel2 for each listed node (one node per thread); per-node seconds."""
         nodes = np.ascontiguousarray(nodes, dtype=np.int64)

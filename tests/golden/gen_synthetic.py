@@ -46,14 +46,81 @@ def make_room_map(W, room, nocc, seed):
     return region, lines, seed_pt
 
 
+# Small walled rooms on grids whose world coordinates are not exact in FP64 (name: origin, spacing, cells a
+# side, seed).  depixelate(cell) = bottom_left + spacing * index rounds at every cell, so |gy| / |gx| of a
+# diagonal cell is not always exactly 1 and whichbin (pointdata.h:432-520) sends some diagonal cells to the
+# sector bin next to the diagonal bin.  os07: the OS-grid origin of the barnsbury drawing with a 0.7 m grid;
+# neg01: a 0.1 grid around (-1000, 1000).  The seeds are ones at which the room has the same visible set as
+# its twin with unit coordinates (the occluder ends are rounded to 6 decimals, so a grazing ray can differ on
+# other seeds); tests/test_noisy_rooms.py checks it.
+NOISY_ROOMS = {
+    "os07": ((530635.696268, 183499.852969), 0.7, 24, 6),
+    "neg01": ((-1000.0, 1000.0), 0.1, 30, 11),
+}
+
+
+def make_noisy_room(origin, spacing, n, seed):
+    """A walled room of n x n filled cells.  The layout is laid on the grid PointMap::setGrid makes (cell centres
+    on multiples of the spacing): with G the grid point nearest `origin`, the border rectangle is
+    [-0.4, n - 0.6]^2 in cell units from G, and three occluders shorter than 1.5 cells sit on cell corners.
+    Coordinates are G + spacing * u rounded to the 6 decimals of the CSV fixtures.  The same (n, seed) gives the
+    same layout in cell units on every grid: origin (0, 0) and spacing 1.0 give the room with exact
+    coordinates.  Returns (region = the lines' bounding box, lines [7][4], fill point in the centre cell)."""
+    rng = np.random.default_rng(seed)
+    lo, hi = -0.4, n - 0.6
+    u = [[lo, lo, hi, lo], [hi, lo, hi, hi], [hi, hi, lo, hi], [lo, hi, lo, lo]]
+    for _ in range(3):
+        c = rng.integers(2, n - 3, size=2) + 0.5
+        a = rng.uniform(0.0, math.pi)
+        h = 0.5 * rng.uniform(0.8, 1.4)
+        d = np.round([h * math.cos(a), h * math.sin(a)], 2)
+        u.append([c[0] - d[0], c[1] - d[1], c[0] + d[0], c[1] + d[1]])
+    u = np.array(u, dtype=np.float64)
+    G = [round(round(origin[0] / spacing) * spacing, 6), round(round(origin[1] / spacing) * spacing, 6)]
+    lines = np.round(np.array(G + G, dtype=np.float64) + spacing * u, 6)
+    region = [float(lines[:, [0, 2]].min()), float(lines[:, [1, 3]].min()),
+              float(lines[:, [0, 2]].max()), float(lines[:, [1, 3]].max())]
+    mid = n // 2 + 0.2
+    fill = (round(G[0] + spacing * mid, 6), round(G[1] + spacing * mid, 6))
+    return region, lines, fill
+
+
+def make_plaza_map(W=1400, seed=14, origin=(0.0, 0.0), spacing=1.0):
+    """An open W x W plaza: border walls and 5 occluders of length <= 1.5 cells within +-30 cells of each of the
+    four points (90, 90), (W - 90, 90), (90, W - 90), (W - 90, W - 90), so that sight lines run the length of
+    the map past the corners' occluders.  Cell units are placed at origin + spacing * u (the default: exact
+    unit coordinates).  Returns (region, lines [24][4], fill point)."""
+    rng = np.random.default_rng(seed)
+    W = float(W)
+    u = [[0.0, 0.0, W, 0.0], [W, 0.0, W, W], [W, W, 0.0, W], [0.0, W, 0.0, 0.0]]
+    for (px, py) in ((90.0, 90.0), (W - 90.0, 90.0), (90.0, W - 90.0), (W - 90.0, W - 90.0)):
+        for _ in range(5):
+            cx, cy = rng.uniform(-29.0, 29.0, size=2)
+            a = rng.uniform(0.0, math.pi)
+            h = 0.5 * rng.uniform(0.5, 1.5)
+            u.append([px + cx - h * math.cos(a), py + cy - h * math.sin(a),
+                      px + cx + h * math.cos(a), py + cy + h * math.sin(a)])
+    u = np.array(u, dtype=np.float64)
+    o = np.array([origin[0], origin[1], origin[0], origin[1]], dtype=np.float64)
+    lines = o + spacing * u
+    region = [origin[0], origin[1], origin[0] + spacing * W, origin[1] + spacing * W]
+    fill = (origin[0] + spacing * 0.5, origin[1] + spacing * 0.5)
+    return region, lines, fill
+
+
 def write_csv(path, lines):
     with open(path, "w") as f:
         f.write("x1,y1,x2,y2\n")
         for l in lines:
-            f.write("%.6f,%.6f,%.6f,%.6f\n" % l)
+            f.write("%.6f,%.6f,%.6f,%.6f\n" % tuple(l))
 
 
 if __name__ == "__main__":
-    W, n, seed, out = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]), sys.argv[4]
+    if sys.argv[1] == "room":   # python tests/golden/gen_synthetic.py room os07 out.csv
+        region, lines, fill = make_noisy_room(*NOISY_ROOMS[sys.argv[2]])
+        write_csv(sys.argv[3], lines)
+        print("fill %.6f,%.6f" % fill)
+        sys.exit(0)
+    W, n, seed, out =int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]), sys.argv[4]
     lmin, lmax = (float(sys.argv[5]), float(sys.argv[6])) if len(sys.argv) > 6 else (0.02, 0.10)
     write_csv(out, make_lines(W, n, seed, lmin, lmax))

@@ -31,6 +31,8 @@ CASES = {
     "syn128": ("inputs/syn128.csv", 1.0, ["0.5,0.5"], True, False, False),
     "syn256mk": ("inputs/syn256.csv", 1.0, ["0.5,0.5"], False, False, False),
     "syn128sd": ("inputs/syn128.csv", 1.0, ["0.5,0.5"], False, False, False),   # step depths only
+    # inexact world coordinates (gen_synthetic.py NOISY_ROOMS: `gen_synthetic.py room os07 inputs/os07.csv`)
+    "os07": ("inputs/os07.csv", 0.7, ["530644.24,183508.64"], True, True, True),
 }
 
 # step depth selections per case (STEPDEPTH -sdt metric|visual -sdp x,y [-sdp ...]); the probe runs

@@ -6,13 +6,135 @@
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <string>
 #include <vector>
 
 #include "../../depthmapx_amd/csrc/kernels/span.hpp"
 
 using namespace dmx;
 
+// ---- `span_check bins`: the per-cell bin decision (span.hpp cell_bin, the makeGraph chunk loop's) on its own.
+static SpanOct make_oct(int q, int cx, int cy, double blx, double bly, double sp) {
+    SpanOct o;
+    o.q = q; o.cx = cx; o.cy = cy; o.blx = blx; o.bly = bly; o.sp = sp;
+    o.c0x = blx + sp * 1.0 * (double)cx;
+    o.c0y = bly + sp * 1.0 * (double)cy;
+    o.obinp = octant_bins(q);
+    return o;
+}
+
+// Unit coordinates: cell_bin against the class from exact integer predicates (tan 30 = 1 / sqrt 3: ratio >= tan 30
+// <=> 3 ind^2 >= depth^2; tan 15 = 2 - sqrt 3: ratio >= tan 15 <=> (2 depth - ind)^2 <= 3 depth^2), every
+// (depth <= 4096, ind <= depth), all 8 octants.
+static long long check_exact_classes(long long& checked) {
+    long long bad = 0;
+    for (int q = 0; q < 8; q++) {
+        const SpanOct o = make_oct(q, 4100, 4100, 0.0, 0.0, 1.0);
+        for (long long d = 1; d <= 4096; d++)
+            for (long long i = 0; i <= d; i++) {
+                const int k = (i == 0) ? 0 : (i == d) ? 4 : (3 * i * i >= d * d) ? 3 : ((2 * d - i) * (2 * d - i) <= 3 * d * d) ? 2 : 1;
+                if (cell_bin(o, (int)d, (int)i) != obin(o.obinp, k)) {
+                    if (bad < 10) fprintf(stderr, "exact class: q %d depth %lld row %lld: cell_bin %d, class %d\n", q, d, i, cell_bin(o, (int)d, (int)i), k);
+                    bad++;
+                }
+                checked++;
+            }
+    }
+    return bad;
+}
+
+struct Coords { const char* name; double ox, oy, sp; };
+// region bottom-left corners and spacings; the grid's bottom-left cell centre comes from PointMap::setGrid
+// (pointdata.cpp:122-171): the first two are the rooms of tests/golden/gen_synthetic.py NOISY_ROOMS
+static const Coords kCoords[] = {
+    {"os07", 530635.42, 183499.82, 0.7},
+    {"neg01", -1000.04, 999.96, 0.1},
+    {"os004", 5.3e5, 1.8e5, 0.04},
+    {"unit", 0.0, 0.0, 1.0},
+    {"os2", 530635.696268, 183499.852969, 2.0},
+};
+static double grid_origin(double b, double sp) {
+    double off = fmod(b, sp);
+    if (off < sp / 2.0) off += sp;
+    if (off > sp / 2.0) off -= sp;
+    return b - off;
+}
+
+// Every in-grid cell of a G x G grid around each of a set of sources, in its octant(s): cell_bin against plain
+// FP64 whichbin(depixelate(cell) - centre).  Diagonal cells (ind == depth) are counted apart.
+static void check_noisy(const Coords& c, int G, long long& cells, long long& bad_off, long long& bad_diag) {
+    const double blx = grid_origin(c.ox, c.sp), bly = grid_origin(c.oy, c.sp);
+    std::mt19937_64 rng(77);
+    std::vector<std::pair<int, int>> src = {{0, 0}, {G - 1, 0}, {0, G - 1}, {G - 1, G - 1}, {G / 2, G / 2}, {1, G - 9}};
+    for (int i = 0; i < 6; i++) src.push_back({(int)(rng() % G), (int)(rng() % G)});
+    for (auto s : src)
+        for (int q = 0; q < 8; q++) {
+            const SpanOct o = make_oct(q, s.first, s.second, blx, bly, c.sp);
+            for (int d = 1; d < G; d++)
+                for (int i = 0; i <= d; i++) {
+                    int hx, hy;
+                    octant_xy(q, s.first, s.second, d, i, hx, hy);
+                    if (hx < 0 || hx >= G || hy < 0 || hy >= G) continue;
+                    const double px = blx + c.sp * 1.0 * (double)hx, py = bly + c.sp * 1.0 * (double)hy;
+                    const int want = whichbin(px - o.c0x, py - o.c0y), got = cell_bin(o, d, i);
+                    cells++;
+                    if (got != want) {
+                        if (i == d) bad_diag++;
+                        else {
+                            if (bad_off < 10) fprintf(stderr, "%s: source (%d, %d) q %d depth %d row %d: cell_bin %d, whichbin %d\n", c.name, s.first, s.second, q, d, i, got, want);
+                            bad_off++;
+                        }
+                    }
+                }
+        }
+}
+
+// diag_offbin_depths against a count over every source and diagonal cell of a small grid
+static int brute_offbin_depths(int G, double blx, double bly, double sp) {
+    std::vector<char> hit(G, 0);
+    for (int x = 0; x < G; x++)
+        for (int y = 0; y < G; y++)
+            for (int q = 0; q < 4; q++) {
+                const SpanOct o = make_oct(q, x, y, blx, bly, sp);
+                for (int d = 1; d < G; d++) {
+                    int hx, hy;
+                    octant_xy(q, x, y, d, d, hx, hy);
+                    if (hx < 0 || hx >= G || hy < 0 || hy >= G) break;
+                    const double px = blx + sp * 1.0 * (double)hx, py = bly + sp * 1.0 * (double)hy;
+                    if (whichbin(px - o.c0x, py - o.c0y) != cell_bin(o, d, d)) hit[d] = 1;
+                }
+            }
+    int n = 0;
+    for (int d = 1; d < G; d++) n += hit[d];
+    return n;
+}
+
+static int main_bins() {
+    long long checked = 0;
+    const long long bad_exact = check_exact_classes(checked);
+    printf("exact classes: cells %lld, mismatches %lld\n", checked, bad_exact);
+    long long bad_off = 0, bad_diag = 0, bad_pre = 0;
+    for (const Coords& c : kCoords) {
+        const int G = 1400;
+        const double blx = grid_origin(c.ox, c.sp), bly = grid_origin(c.oy, c.sp);
+        long long cells = 0, off = 0, diag = 0;
+        check_noisy(c, G, cells, off, diag);
+        const int pre = diag_offbin_depths(G, G, blx, bly, c.sp);
+        const int pre_small = diag_offbin_depths(48, 48, blx, bly, c.sp), brute_small = brute_offbin_depths(48, blx, bly, c.sp);
+        printf("%s (bottom-left %.17g %.17g, spacing %g): cells %lld, off-diagonal mismatches %lld, diagonal mismatches %lld; "
+               "depths with a diagonal cell off its bin: %d of %d (48^2: %d, counted %d)\n", c.name, blx, bly, c.sp, cells, off,
+               diag, pre, G - 1, pre_small, brute_small);
+        bad_off += off;
+        bad_diag += diag;
+        // the precheck covers every source: none found by it means none in the sample, and it equals the count
+        bad_pre += (pre == 0 && diag != 0) + (pre_small != brute_small);
+    }
+    printf("noisy off-diagonal mismatches %lld\nnoisy diagonal mismatches %lld\nprecheck mismatches %lld\n", bad_off, bad_diag, bad_pre);
+    return (bad_exact || bad_off || bad_pre) ? 1 : (bad_diag ? 2 : 0);
+}
+
 int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "bins") return main_bins();
     const int trials = argc > 1 ? atoi(argv[1]) : 2000;
     std::mt19937_64 rng(argc > 2 ? atoll(argv[2]) : 2026);
     std::uniform_real_distribution<double> U(0.0, 1.0);

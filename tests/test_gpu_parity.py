@@ -16,7 +16,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 pytestmark = pytest.mark.gpu
 
-MK_CASES = ["kat", "syn16", "syn32", "gallery", "syn64", "barnsbury", "syn256mk"]
+# os07: a room on inexact world coordinates (tests/golden/gen_synthetic.py NOISY_ROOMS).  The reference moves some of
+# its diagonal cells to the sector bins next to the diagonal bins; the kernel does not (known divergence, DESIGN.md
+# section 2, "Inexact world coordinates"; tests/test_gpu_longsight.py checks what does hold on this map)
+OS07 = pytest.param("os07", marks=pytest.mark.xfail(strict=True, reason="known divergence (DESIGN.md section 2, "
+                    "'Inexact world coordinates'): every diagonal cell takes the diagonal bin"))
+MK_CASES = ["kat", "syn16", "syn32", "gallery", "syn64", "barnsbury", "syn256mk", OS07]
 VGA_CASES = ["kat", "syn16", "syn32", "gallery", "syn64", "barnsbury", "syn128"]
 VGA_RTOL = 1e-6
 
@@ -424,7 +429,7 @@ def test_metric_stepdepth_errors(ctx):
 CHUNK_CASES = ["kat", "syn16", "syn32", "gallery", "syn64"]
 
 
-@pytest.mark.parametrize("name", CHUNK_CASES)
+@pytest.mark.parametrize("name", CHUNK_CASES + [OS07])
 def test_gpu_graph_chunk_bytes_match_reference(ctx, name):
     """VISPREP's output: the PointMap chunk written from the GPU graph is byte-identical to the one
     the reference writes (PointMap::write)."""

@@ -7,7 +7,7 @@ import pytest
 from golden_io import case_input_lines, load_case, node_digests, roundtrip_runs
 from pyoracle import OracleMap
 
-CASES = ["kat", "syn16", "syn32", "gallery", "syn64", "barnsbury"]
+CASES = ["kat", "syn16", "syn32", "gallery", "syn64", "barnsbury", "os07"]
 
 
 def _oracle(meta, threads=8):
@@ -46,7 +46,7 @@ def test_makegraph_matches_reference(name):
     np.testing.assert_array_equal(node_digests(g["bins"], g["runs"]), A["digests"])
 
 
-@pytest.mark.parametrize("name", ["kat", "syn16", "syn32", "gallery", "syn64"])
+@pytest.mark.parametrize("name", ["kat", "syn16", "syn32", "gallery", "syn64", "os07"])
 def test_vga_global_matches_reference_bitexact(name):
     meta, A = load_case(name)
     om = _oracle(meta)
@@ -64,7 +64,7 @@ def test_vga_global_barnsbury_bitexact():
     np.testing.assert_array_equal(out.view(np.uint32), A["vga"].view(np.uint32))
 
 
-@pytest.mark.parametrize("name", ["syn32", "gallery", "syn64"])
+@pytest.mark.parametrize("name", ["syn32", "gallery", "syn64", "os07"])
 def test_graph_file_roundtrip_quirk(name):
     """VGA in the CLI pipeline runs on the re-read .graph whose runs went through the lossy 4-bit
     row shift; the reference's post-round-trip VGA columns (vga_rt) are reproduced by
