@@ -256,6 +256,7 @@ static int makegraph_impl(dmx_ctx* ctx, dmx_pointmap* pm, double maxdist, int bo
             P.sym_ho = sym_pass ? g->sym_ho.p : nullptr;
             // the shortest span taken (DMX_MK_SPAN: A/B hook; DMX_MK_NOSPAN: every depth cell by cell)
             P.spans = getenv("DMX_MK_NOSPAN") ? 0 : (getenv("DMX_MK_SPAN") ? std::max(1, atoi(getenv("DMX_MK_SPAN"))) : MK_SPAN_MIN);
+            P.wall = pm->wall_sides;   // closed sides: spans along the outer wall (DMX_MK_NOWALL: none, upload_pointmap)
             HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
             if (todo > 0) {
                 HIPCHK(dP.alloc(1));
@@ -343,8 +344,9 @@ static int makegraph_impl(dmx_ctx* ctx, dmx_pointmap* pm, double maxdist, int bo
             VLOG("makegraph merges: %llu (%llu with one block), %.2f blocks and %.2f gaps a merge\n", st[18], st[19],
                  st[18] ? (double)st[20] / st[18] : 0.0, st[18] ? (double)st[21] / st[18] : 0.0);
             VLOG("makegraph spans: %.1f%% of the clocks; %llu spans over %llu depths (%.1f each), %llu of %llu visible cells "
-                 "(%.1f%%)\n", 100 * st[22] / tot, st[23], st[24], st[23] ? (double)st[24] / st[23] : 0.0, st[25], st[1],
-                 st[1] ? 100.0 * st[25] / st[1] : 0.0);
+                 "(%.1f%%); %llu wall spans over %llu depths (closed sides 0x%x)\n", 100 * st[22] / tot, st[23], st[24],
+                 st[23] ? (double)st[24] / st[23] : 0.0, st[25], st[1], st[1] ? 100.0 * st[25] / st[1] : 0.0, st[4], st[5],
+                 (unsigned)pm->wall_sides);
             VLOG("makegraph span parts: rows' class ends and open state %.1f%%, gap depth searches %.1f%%, class pieces "
                  "%.1f%%, the rest (setup, examined, sums) %.1f%% of the clocks; %llu row chunks, %llu (chunk, gap) pairs, "
                  "%llu of them with no visible row\n", 100 * st[26] / tot, 100 * st[27] / tot, 100 * st[28] / tot,

@@ -219,6 +219,8 @@ struct dmx_pointmap {
     // device copies (per context device; refreshed when the host state changes)
     int uploaded_for = -1;
     uint64_t version = 1, uploaded_version = 0;
+    int wall_sides = 0;         // closed sides of the grid (closed_sides), as uploaded
+    bool uploaded_nowall = false;   // DMX_MK_NOWALL at the upload (the clean distances depend on it)
     int64_t nnodes = 0;
     std::vector<int32_t> node_cell;
     DevBuf<uint32_t> d_cellw;
@@ -360,14 +362,26 @@ int prepare_merges(dmx_graph* g) {
 // word, in place of the unused segment offset, its clean distance -- the Chebyshev distance to the nearest cell
 // that is not clean or lies outside the grid.  Two raster passes of the 8-neighbour chamfer (Rosenfeld-Pfaltz),
 // exact for the Chebyshev metric; the outside enters as each cell's distance to the border.
-static void clean_distance(const PointMapHost& h, std::vector<uint32_t>& cellw) {
+// On a closed side (closed_sides) the outside does not enter, and the cells of the side's outermost line that are
+// not FILLED and hold exactly one piece are not dirty: they carry a distance through the passes like a clean cell
+// (so the distance stays the exact Chebyshev distance to what is left dirty) without storing one.  The kernel
+// handles those cells itself (makegraph.hip, wall mode).
+static void clean_distance(const PointMapHost& h, std::vector<uint32_t>& cellw, int sides) {
     const int W = h.cols(), H = h.rows();
     std::vector<uint32_t> d((size_t)W * H);
     for (int x = 0; x < W; x++)
         for (int y = 0; y < H; y++) {
             const size_t c = (size_t)x * H + y;
             const bool clean = (cellw[c] & 0xFFu) == 1u;   // FILLED, 0 pieces
-            d[c] = clean ? (uint32_t)std::min(std::min(x + 1, y + 1), std::min(W - x, H - y)) : 0u;
+            const bool online = ((sides & 1) && x == 0) || ((sides & 2) && x == W - 1) || ((sides & 4) && y == 0) ||
+                                ((sides & 8) && y == H - 1);
+            const bool wallc = online && (cellw[c] & 0xFFu) == 2u;   // not FILLED, 1 piece
+            uint32_t b = CELL_DIST_MAX;
+            if (!(sides & 1)) b = std::min(b, (uint32_t)(x + 1));
+            if (!(sides & 2)) b = std::min(b, (uint32_t)(W - x));
+            if (!(sides & 4)) b = std::min(b, (uint32_t)(y + 1));
+            if (!(sides & 8)) b = std::min(b, (uint32_t)(H - y));
+            d[c] = (clean || wallc) ? b : 0u;
         }
     for (int x = 0; x < W; x++)
         for (int y = 0; y < H; y++) {
@@ -401,10 +415,28 @@ static void clean_distance(const PointMapHost& h, std::vector<uint32_t>& cellw) 
         if ((cellw[c] & 0xFFu) == 1u) cellw[c] = (std::min(d[c], CELL_DIST_MAX) << 8) | 1u;
 }
 
+// The closed sides of the grid: bit 0 x = 0, 1 x = cols - 1, 2 y = 0, 3 y = rows - 1.  A side is closed when every
+// cell of its outermost line, corners aside, is not FILLED (a drawing with a border line: makeGraph's spans run
+// along such a wall).
+static int closed_sides(int W, int H, const std::vector<uint32_t>& cellw) {
+    if (W < 3 || H < 3) return 0;
+    int sides = 15;
+    for (int y = 1; y < H - 1; y++) {
+        if (cellw[(size_t)y] & 1u) sides &= ~1;
+        if (cellw[(size_t)(W - 1) * H + y] & 1u) sides &= ~2;
+    }
+    for (int x = 1; x < W - 1; x++) {
+        if (cellw[(size_t)x * H] & 1u) sides &= ~4;
+        if (cellw[(size_t)x * H + H - 1] & 1u) sides &= ~8;
+    }
+    return sides;
+}
+
 int upload_pointmap(dmx_ctx* ctx, dmx_pointmap* pm) {
     PointMapHost& h = *pm->host;
     if (!h.lines_blocked()) h.block_lines();
-    if (pm->uploaded_version == pm->version && pm->uploaded_for == ctx->device) return DMX_OK;
+    const bool nowall = getenv("DMX_MK_NOWALL") != nullptr;   // A/B hook: no closed sides, the clean distances of before
+    if (pm->uploaded_version == pm->version && pm->uploaded_for == ctx->device && pm->uploaded_nowall == nowall) return DMX_OK;
     if (pm->uploaded_for >= 0 && pm->uploaded_for != ctx->device) {
         // another device's copies: release them (DevBuf::alloc would otherwise reuse the pointers)
         pm->d_cellw.reset(); pm->d_segs.reset(); pm->d_node_cell.reset(); pm->d_cell_node.reset();
@@ -431,7 +463,9 @@ int upload_pointmap(dmx_ctx* ctx, dmx_pointmap* pm) {
         }
     }
     pm->nnodes = (int64_t)pm->node_cell.size();
-    clean_distance(h, cellw);
+    pm->wall_sides = nowall ? 0 : closed_sides(h.cols(), h.rows(), cellw);
+    pm->uploaded_nowall = nowall;
+    clean_distance(h, cellw, pm->wall_sides);
     // seed bitmap for the BFS: 1 = not a filled cell (or padding), 8x8 tiles
     const int tw = (h.cols() + 7) / 8, th = (h.rows() + 7) / 8;
     std::vector<unsigned long long> seed((size_t)tw * th, ~0ull), nonexp((size_t)tw * th, 0ull);

@@ -48,6 +48,8 @@ constexpr int MK_GCAP0 = 16, MK_BCAP0 = 32;   // first-pass LDS gap / block capa
 // 1: 3.23 / 9.61 s, 2: 3.17 / 9.02, 4: 3.11 / 8.61, 8: 3.11 / 8.75 (profiles/r6_span_ab.jsonl); with the gap skip
 // 3: 2.884 / 8.261, 4: 2.886 / 8.244, 5: 2.881 / 8.255, 6: 2.889 / 8.306 (r6_span_ab2.jsonl, tags s3..s6)
 constexpr int MK_SPAN_MIN = 4;
+constexpr int MK_NOWALL = 1 << 28;   // wall row / far-line depth of an octant whose side is not closed
+constexpr int MK_NOCAND = 1 << 24;   // clean distance of a candidate the span certificate leaves out (on or past the wall)
 // open-run state of rows 0 .. MK_OPEN_LDS-1 lives in LDS, of farther rows (grids above ~1020 cells a
 // side) in per-wave scratch memory: rows past 1024 are reached only by sight lines longer than 1024
 // cells, and a full-length LDS array would cost a 2000^2 grid a quarter of its waves
@@ -109,6 +111,10 @@ struct MakeGraphParams {
     // occluder-free depth spans (span.hpp): the shortest span taken, in depths (0: off); the cell words of FILLED
     // cells without an occluder piece carry their clean distance (common.hpp cell_span_dist)
     int spans;
+    // closed sides of the grid (bit 0 x = 0, 1 x = cols - 1, 2 y = 0, 3 y = rows - 1; upload_pointmap): every cell of
+    // the side's outermost line, corners aside, is not FILLED, and the clean distances ignore the line's cells that
+    // hold exactly one piece and the outside behind them -- spans run along such a wall (wall mode below)
+    int wall;
 };
 
 // phase clocks (profile builds of a run only; wave-uniform scalar reads)
@@ -439,6 +445,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
     unsigned long long mst[4] = {0, 0, 0, 0};   // PROF: merges, one-block merges, blocks, gaps at merges
     unsigned long long spst[6] = {0, 0, 0, 0, 0, 0};   // PROF: spans, span depths, span cells, row chunks, (chunk, gap)
                                                        // pairs, pairs with no visible row
+    unsigned long long wsp[2] = {0, 0};   // PROF: wall-mode spans, their depths
     unsigned long long tmark = PROF ? __builtin_amdgcn_s_memtime() : 0;
 
     for (;;) {
@@ -526,6 +533,14 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
                 obinp = __builtin_amdgcn_readfirstlane(obinp);
             }
 #define OBIN(k) ((int)__builtin_amdgcn_ubfe(obinp, (unsigned)(6 * (k)), 6u))
+            // the wall row on the octant's high-row side: the outermost cell line there, when that side is closed
+            int Bq = MK_NOWALL;
+            {
+                const int bside = (q < 4) ? (q <= 1 ? 8 : 4) : ((q & 1) ? 2 : 1);
+                const int bdist = (q < 4) ? (q <= 1 ? P.rows - 1 - cy : cy) : ((q & 1) ? P.cols - 1 - cx : cx);
+                if (P.wall & bside) Bq = bdist;
+                Bq = __builtin_amdgcn_readfirstlane(Bq);
+            }
             int depth = 0;
             MK_T(9);
             // cell word of candidate t = lane of the next depth, loaded while this depth finishes: the
@@ -837,7 +852,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
                             put_block(slot, (ta < tb) ? make_double2(ta - 1e-10, tb + 1e-10) : make_double2(tb - 1e-10, ta + 1e-10));
                         }
                     }
-                    if (valid) lmin = min(lmin, ingrid ? cell_span_dist(w) : 0);
+                    if (valid) {
+                        // (a wall cell with its one piece and the rows outside behind it stay out of the certificate)
+                        const bool wallc = ind >= Bq && (!ingrid || (w & 0xFFu) == 2u);
+                        lmin = min(lmin, wallc ? MK_NOCAND : ingrid ? cell_span_dist(w) : 0);
+                    }
                     hasgaps |= (ballot(ingrid) != 0ull);
                     MK_T(2);
                     // ---- visible cells: bins, moments (reference order), run tracking
@@ -959,14 +978,94 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
                 // spread over the lanes; a row's runs, bin counts and far distances come per (gap, ratio class)
                 // interval, only the first moment's square roots per cell.
                 // (expect false: the register allocator weighs the span's loops below the candidate loop's)
-                if (__builtin_expect(spans && !failed && L.misc[1] == 0 && ballot(lmin < span_min + 2) == 0ull, 0)) {
+                // Along a closed side's wall (row Bq, one piece a cell; span.hpp): the clean distances ignore the wall
+                // and the outside behind it, and lmin its candidates, so the lemma leaves one kind of visited cell
+                // that is not clean: the wall cell of each depth.  A span whose front is below the wall ends before
+                // the last gap reaches it.  A span entered with the wall cell's block pending ("wall mode") replays
+                // every depth's block with a depth a lane and is cut at the first depth that leaves the trim branch.
+                // Behind a closed far side the clean distances do not see the far line: no span passes Aq - 2.
+                if (__builtin_expect(spans && !failed && L.misc[1] <= (Bq < MK_NOWALL ? 1 : 0) && ballot(lmin < span_min + 2) == 0ull, 0)) {
                     int mind = lmin;
 #if MK_WFRED
                     mind = __ockl_wfred_min_i32(mind);
 #else
                     for (int off = 32; off >= 1; off >>= 1) mind = min(mind, __shfl_xor(mind, off));
 #endif
-                    const int d0 = depth + 1, d1 = depth + (mind - 2);
+                    int Aq = MK_NOWALL;   // the depth of the far line, when that side is closed
+                    {
+                        const int aside = (q < 4) ? ((q & 1) ? 2 : 1) : (q >= 6 ? 8 : 4);
+                        const int adist = (q < 4) ? ((q & 1) ? P.cols - 1 - cx : cx) : (q >= 6 ? P.rows - 1 - cy : cy);
+                        if (P.wall & aside) Aq = adist;
+                    }
+                    const bool wallmode = L.misc[1] != 0;
+                    const int d0 = depth + 1;
+                    int d1 = min(depth + (min(mind, 1 << 20) - 2), Aq - 2);
+                    unsigned long long exs = 0;   // cells examined (stats[0]) over the span, this lane's share
+                    double wall_e = 0.0;          // wall mode: the last gap's end after the span's last merge
+                    if (wallmode) {
+                        // entry: the last gap visited rows below the wall and the wall cell (the pending block is
+                        // that cell's: every other candidate is clean), and the earlier gaps are not degenerate
+                        const int la = L.ga[ng - 1], lb = la + (L.gpre[ng] - L.gpre[ng - 1]) - 1;
+                        bool degen = false;
+                        for (int g = lane; g < ng - 1; g += 64) {
+                            const double2 z = L.gaps[g];
+                            degen |= !(z.y > z.x + 1e-10);
+                        }
+                        if (!(la <= Bq - 1 && lb >= Bq) || ballot(degen) != 0ull) d1 = depth;
+                        const double gs_ = L.gaps[ng - 1].x;
+                        double Ec = L.gaps[ng - 1].y;
+                        for (int jb = depth; jb <= d1; jb += 64) {   // lane j - jb: the merge of depth j's block, and
+                            const int j = jb + lane;                 // (past the entry depth) depth j's visit before it
+                            const bool act = j <= d1;
+                            double kx = INFINITY, ky = INFINITY;
+                            bool ok = false;
+                            if (act) {
+                                int hx, hy;
+                                octant_cell(q, cx, cy, j, Bq, hx, hy);
+                                if (hx >= 0 && hx < P.cols && hy >= 0 && hy < P.rows) {
+                                    const uint32_t w = P.cellw[hx * P.rows + hy];
+                                    if ((w & 0xFFu) == 2u) {   // not FILLED, one piece: its block, as the chunk loop adds it
+                                        const double* sg = P.segs + 4 * (size_t)cell_seg_off(w);
+                                        const double ta = tanify(c0x, c0y, sg[0], sg[1], q), tb = tanify(c0x, c0y, sg[2], sg[3], q);
+                                        kx = (ta < tb) ? ta - 1e-10 : tb - 1e-10;
+                                        ky = (ta < tb) ? tb + 1e-10 : ta + 1e-10;
+                                        ok = true;
+                                    }
+                                }
+                            }
+                            double Ei = kx;   // min(e, kx) as collectgarbage takes it: prefix minimum over the depths
+                            for (int o = 1; o < 64; o <<= 1) {
+                                const double t = __shfl_up(Ei, o);
+                                if (lane >= o && t < Ei) Ei = t;
+                            }
+                            double Ep = __shfl_up(Ei, 1);
+                            if (lane == 0 || Ec < Ep) Ep = Ec;
+                            if (Ec < Ei) Ei = Ec;
+                            ok = ok && wall_merge_ok(gs_, Ep, Ei, kx, ky);
+                            int T = 0;
+                            if (j > depth) {
+                                const double Eu = Ep <= 1.0 ? Ep : 1.0;   // (lanes past a failed depth hold no gap end)
+                                int F = 0, nl = 0;
+                                for (int g = 0; g < ng - 1; g++) {
+                                    const double2 z = L.gaps[g];
+                                    const int lo = gap_lo(z.x, j), b = min(gap_hi(z.y, j), j), a = max(lo, F);
+                                    T += (b >= a) ? (b - a + 1) : 0;
+                                    if (b >= lo) F = max(F, b);
+                                }
+                                ok = wall_visit_ok(gs_, Eu, F, j, Bq, nl) && ok;
+                                T += nl;
+                            }
+                            const unsigned long long fm = ballot(act && !ok);
+                            const int nok = fm ? (__ffsll((long long)fm) - 1) : min(64, d1 - jb + 1);
+                            if (lane < nok) exs += (unsigned long long)T;
+                            if (nok > 0) Ec = __shfl(Ei, nok - 1);
+                            if (fm) { d1 = jb + nok - 1; break; }
+                        }
+                        wall_e = Ec;
+                    } else if (Bq < MK_NOWALL) {
+                        d1 = wall_below_last(L.gaps[ng - 1].y, Bq, d0, d1);
+                    }
+                  if (d1 - d0 + 1 >= span_min) {
                     if (far_rows) __syncthreads(); else wave_sync();   // this depth's open-row stores
                     SpanOct so;
                     so.q = q; so.cx = cx; so.cy = cy; so.blx = P.blx; so.bly = P.bly; so.sp = sp; so.c0x = c0x; so.c0y = c0y;
@@ -983,7 +1082,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
 #endif
                     }
                     wave_sync();
-                    const int R0 = max(0, gap_cl(L.gaps[0].x, d0)), R1 = min(d1, gap_ch(L.gaps[ng - 1].y, d1));
+                    const int R0 = max(0, gap_cl(L.gaps[0].x, d0)), R1 = min(d1, wallmode ? Bq - 1 : gap_ch(L.gaps[ng - 1].y, d1));
                     int nsp = 0;   // this lane's visible cells in the span
                     for (int rb = R0; rb <= R1; rb += 64) {
                         if (COUNT || PROF) nchunks++;
@@ -1006,7 +1105,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
                         if (PROF) spst[3]++;
                         MK_T(11);
                         for (int g = ng - 1; g >= 0; g--) {   // later gaps first: the row's depths in order
-                            const double2 z = L.gaps[g], iz = L.gaps2[g];
+                            double2 z = L.gaps[g], iz = L.gaps2[g];
+                            // wall mode: the last gap's centre reaches row Bq - 1 at every depth (checked above) and the
+                            // rows end there, so its upper bound is vacuous: the octant's own, ind <= depth
+                            if (wallmode && g == ng - 1) { z.y = 1.0; iz.y = 1.0; }
                             const double gs_ = z.x, ge_ = z.y;
 #if MK_SPAN_GSKIP
                             // rows below cl(s, d0) or above ch(e, d1) see no depth of the span in this gap
@@ -1118,8 +1220,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
                         }
                     }
                     // cells examined (stats[0]): the visit ranges of every span depth, one depth a lane
-                    unsigned long long exs = 0;
-                    for (int db = d0; db <= d1; db += 64) {
+                    for (int db = d0; db <= d1 && !wallmode; db += 64) {   // (wall mode: counted by its depth pass)
                         const int d = db + lane;
                         int F = 0, T = 0;
                         for (int g = 0; g < ng; g++) {
@@ -1147,11 +1248,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
                     if (PROF) { spst[0]++; spst[1] += (unsigned long long)(d1 - d0 + 1); spst[2] += (unsigned long long)__shfl(nsp, 0); }
 #endif
                     if (COUNT || PROF) nsteps++;
+                    if (wallmode) {   // the span's blocks are merged: the last gap's end, no block pending
+                        if (lane == 0) { L.gaps[ng - 1].y = wall_e; L.misc[1] = 0; }
+                        if (PROF) { wsp[0]++; wsp[1] += (unsigned long long)(d1 - d0 + 1); }
+                    }
                     depth = d1;
                     dq = depth;
                     if (nA > P.capA) { failed = true; if (lane == 0) atomicOr(P.error, KERR_STAGE_CAPACITY); }
                     // the open-row stores (LDS; scratch rows past MK_OPEN_LDS) before the next depth reads them
                     if (far_rows) __syncthreads(); else wave_sync();
+                  }
                     MK_T(10);
                 }
                 // prefetch: candidate t = lane of depth + 1 under the current gap list (few-gap case)
@@ -1451,6 +1557,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
                 for (int i = 0; i < 3; i++) atomicAdd(&P.stats[23 + i], spst[i]);
                 for (int i = 0; i < 3; i++) atomicAdd(&P.stats[26 + i], cyc[11 + i]);
                 for (int i = 0; i < 3; i++) atomicAdd(&P.stats[29 + i], spst[3 + i]);
+                for (int i = 0; i < 2; i++) atomicAdd(&P.stats[4 + i], wsp[i]);
             }
             P.attrs[k * 3 + 0] = (float)nsize;
             P.attrs[k * 3 + 1] = m1f;
@@ -1460,6 +1567,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
         for (int i = 0; i < 14; i++) cyc[i] = 0;
         for (int i = 0; i < 4; i++) mst[i] = 0;
         for (int i = 0; i < 6; i++) spst[i] = 0;
+        wsp[0] = wsp[1] = 0;
         MK_T(7);
     }
 }

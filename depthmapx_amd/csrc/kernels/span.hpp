@@ -193,4 +193,36 @@ DMX_SPAN_HD inline void span_row_gap(int ind, double s, double e, bool has_prev,
     }
 }
 
+// ---- spans along the map's outer wall (makegraph.hip "wall mode"; host test tests/span/wall_check.cpp)
+// The outermost cell line on the octant's high-row side, row B, holds one occluder piece a cell.  At depth j the
+// last gap [s, e_{j-1}] visits cell (j, B); its piece adds the block K_j = [kx_j, ky_j], which collectgarbage
+// merges by trimming the last gap's end: e_j = min(e_{j-1}, kx_j), every earlier gap unchanged.  kx_j depends on
+// the cell alone, so a span of such depths is replayed with a depth a lane: e_j is a prefix minimum, and each
+// depth checks, against the sieve's own expressions, that the walk really takes that branch.
+
+// The merge of block [kx, ky] into a gap list whose last gap is [s, ep] (ei = min(ep, kx)) only trims that gap's
+// end (sparksieve2.cpp:89-132 with one block; the earlier gaps end below s and are not degenerate):
+// kx > s, so the start stays; ky >= ep, so no gap is created; the trimmed gap survives (ei > s + 1e-10).
+DMX_SPAN_HD inline bool wall_merge_ok(double s, double ep, double ei, double kx, double ky) {
+    return kx > s + 1e-10 && ky >= ep && ei > s + 1e-10;
+}
+// Depth j's visit of the last gap [s, ep], F the last row visited by the earlier gaps: those stay below the wall
+// (F <= B - 1), the gap visits the wall cell (a <= B <= b) and every row up to B - 1 is inside its centre
+// (ch >= B - 1).  n: the rows it visits (the wall cell and the rows outside the grid count as examined).
+DMX_SPAN_HD inline bool wall_visit_ok(double s, double ep, int F, int j, int B, int& n) {
+    const int lo = gap_lo(s, j), b = gap_b(ep, j), a = lo > F ? lo : F;
+    n = b - a + 1;
+    return F <= B - 1 && a <= B && b >= B && gap_ch(ep, j) >= B - 1;
+}
+// The last depth j in [d0 - 1, d1] at which the gap ending at e stays below row B (b(e, j) <= B - 1; b is
+// non-decreasing in j): a span without the wall ends there.
+DMX_SPAN_HD inline int wall_below_last(double e, int B, int d0, int d1) {
+    int c = clamp_est(floor(((double)B - 0.5) / e - 0.5), d0 - 1, d1);
+    const int m = B - 1 < d1 ? B - 1 : d1;   // b(e, j) <= j
+    if (c < m) c = m;
+    while (c < d1 && gap_b(e, c + 1) <= B - 1) c++;
+    while (c >= d0 && gap_b(e, c) > B - 1) c--;
+    return c;
+}
+
 }  // namespace dmx
