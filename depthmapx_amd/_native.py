@@ -55,6 +55,7 @@ SIGNATURES = {
     "dmx_vga_thruvision": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp]),
     "dmx_vga_isovist": (_i32, [_vp, _vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "dmx_ctx_last_isovist": (_i32, [_vp, _vp, _vp, _vp]),
+    "dmx_isovists": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
     "dmx_chunk_occlusion": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "dmx_chunk_set_occlusion": (_i32, [_vp, _vp, _vp, _vp]),
     "dmx_vga_metric": (_i32, [_vp, _vp, _dbl, _i32, _i64, _i64, _vp]),

@@ -39,6 +39,7 @@
 #include "kernels/vga_ordered.hip"
 #include "kernels/thruvision.hip"
 #include "kernels/isovist.hip"
+#include "kernels/isovist_points.hip"
 
 using namespace dmx;
 
@@ -722,6 +723,7 @@ int dmx_ctx_last_timing(dmx_ctx* c, double* mk, double* vga) {
 #include "api/vga_other.hip"
 #include "api/thruvision.hip"
 #include "api/isovist.hip"
+#include "api/isovist_points.hip"
 #include "api/stepdepth.hip"
 #include "api/chunk.hip"
 #include "api/graphfile.hip"

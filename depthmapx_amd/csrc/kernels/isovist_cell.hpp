@@ -1,7 +1,8 @@
 // isovist_cell.hpp -- the isovist of one cell centre, one source for the host and the HIP kernel
 // (all functions are __host__ __device__; plain g++ compiles it too).  Compile with -ffp-contract=off.
 //
-// Restates, for the full circle (startangle == endangle):
+// isovist_cell restates, for the full circle (startangle == endangle) at a cell centre, and isovist_point for any
+// point and any (startangle, endangle):
 //   Isovist::makeit                      salalib/isovist.cpp:31-120
 //   Isovist::make / drawnode / addBlock  salalib/isovist.cpp:146-268
 //   Isovist::setData                     salalib/isovist.cpp:270-335
@@ -415,6 +416,99 @@ DMX_HD int isovist_cell(const IsoTree& T, IsoStore& S, const IsoGrid& G, double 
                 if (iso_dist(prev_end, centre) < iso_dist(fs, centre)) occlusion(prev_end, occluded);
                 else occlusion(fs, occluded);
             }
+        }
+    }
+    A.close(centre);
+    const double sc = 2.0 / fabs(A.area);
+    const Vec2 centroid{A.cx * sc, A.cy * sc};
+    Vec2 drift{centroid.x - centre.x, centroid.y - centre.y};
+    const double driftmag = iso_len(drift);
+    drift = iso_normalise(drift);
+    const double driftang = iso_angle(drift);
+    out8[0] = (float)A.area;
+    if (!simple) {
+        out8[1] = (float)(4.0 * ISO_PI * A.area / (perimeter * perimeter));
+        out8[2] = (float)(180.0 * driftang / ISO_PI);
+        out8[3] = (float)driftmag;
+        out8[4] = (float)A.max_radial;
+        out8[5] = (float)A.min_radial;
+        out8[6] = (float)occluded_perimeter;
+        out8[7] = (float)perimeter;
+    }
+    return ISO_OK;
+}
+
+// One isovist at any point of the drawing, full circle or view cone: Isovist::makeit(root, centre, region,
+// startangle, endangle) (isovist.cpp:31-120) and setData over its m_poly, which MetaGraph::makeIsovist
+// (mgraph.cpp:491-521) runs per point.  tolerance = max(region.width(), region.height()) * 1e-9.
+//   complete    startangle == endangle, or (0, 2 pi): one gap (0, 2 pi), no centre vertex
+//   start > end the cone spans angle 0: gaps (0, end) and (start, 2 pi); the centre is pushed once, before the first
+//               block whose startangle compares equal to the cone's
+//   otherwise   one gap (start, end) ("parity"); the centre is pushed after the last block, before the closing test
+// The occlusion bins of VGAIsovist::run are not made here.  vsink.begin(n) is called once with an upper bound of
+// the pushes that follow (2 nb + 2: at most two a block, the centre, the closing vertex), then vsink.push(p) for
+// every m_poly.push_back in order.  out8 as for isovist_cell.  Returns ISO_OK or the capacity flags; on a capacity
+// error nothing has been written and the sink has not been begun.
+template <class VSink>
+DMX_HD int isovist_point(const IsoTree& T, IsoStore& S, double tolerance, Vec2 centre, double startangle,
+                         double endangle, bool simple, float* out8, VSink& vsink) {
+    bool complete = false;
+    if (startangle == endangle || (startangle == 0.0 && endangle == 2.0 * ISO_PI)) {
+        startangle = 0.0;
+        endangle = 2.0 * ISO_PI;
+        complete = true;
+    }
+    bool parity = false;
+    int err = 0;
+    S.ng = 0;
+    S.nb = 0;
+    S.maxg = 0;
+    bool added;
+    if (startangle > endangle) {
+        if (iso_gap_insert(S, 0.0, endangle, 0, &added) < 0 || iso_gap_insert(S, startangle, 2.0 * ISO_PI, 0, &added) < 0)
+            return ISO_GAP_CAPACITY;
+    } else {
+        parity = true;
+        if (iso_gap_insert(S, startangle, endangle, 0, &added) < 0) return ISO_GAP_CAPACITY;
+    }
+    if (!iso_walk(T, S, centre, &err)) return err;
+
+    IsoAccum A;
+    A.area = 0.0; A.cx = 0.0; A.cy = 0.0; A.max_radial = 0.0; A.min_radial = 0.0; A.n = 0;
+    A.first = Vec2{0, 0}; A.prev = Vec2{0, 0};
+    double perimeter = 0.0, occluded_perimeter = 0.0;
+    vsink.begin(2 * S.nb + 2);
+    auto poly = [&](Vec2 p) {   // m_poly.push_back(p)
+        A.point(centre, p);
+        vsink.push(p);
+    };
+    bool markedcentre = false;
+    Vec2 prev_end{0, 0};
+    for (int i = 0; i < S.nb; i++) {
+        const int bi = S.border(i);
+        const Vec2 sp{S.bf(bi, 2), S.bf(bi, 3)}, ep{S.bf(bi, 4), S.bf(bi, 5)};
+        if (!complete && !markedcentre && !parity && S.bf(bi, 0) == startangle) {
+            poly(centre);
+            markedcentre = true;
+        }
+        if (i != 0 && !iso_approxeq(prev_end, sp, tolerance)) {
+            poly(sp);
+            const double occluded = iso_dist(prev_end, sp);
+            perimeter += occluded;
+            occluded_perimeter += occluded;
+        }
+        poly(ep);
+        perimeter += iso_dist(sp, ep);
+        prev_end = ep;
+    }
+    if (!complete && parity) poly(centre);   // "if parity is true, the centre point must be last not first"
+    if (S.nb) {
+        const Vec2 fs{S.bf(S.border(0), 2), S.bf(S.border(0), 3)};
+        if (!iso_approxeq(prev_end, fs, tolerance)) {
+            poly(fs);
+            const double occluded = iso_dist(prev_end, fs);
+            perimeter += occluded;
+            occluded_perimeter += occluded;
         }
     }
     A.close(centre);

@@ -59,6 +59,20 @@ constexpr int kIsoWavesPerCu = 8;
 // pool entries (8 bytes) per node the first launch reserves for occlusion pixels; a pool found too small is
 // enlarged to what the cursor counted and the launch repeated
 constexpr int kIsoPoolPerNode = 48;
+// isovists at arbitrary points (isovist_points_kernel, dmx_isovists).  Polygon pool: vertices (16 bytes) a point
+// the first launch reserves; a point takes 2 nb + 2 of them (syn32's points hold 30 blocks on average and reserve
+// 62, the 1000^2 benchmark map's cell centres 90 vertices and reserve 92), and a pool found too small is enlarged
+// to what the cursor counted and the launch repeated.  Hook: DMX_ISO_VPOOL (tests shrink it to 1).
+constexpr int kIsoVertexPoolPerPoint = 128;
+// workgroups (of one wave) per CU, as kIsoWavesPerCu, capped by the occupancy query: the kernel's 166 VGPRs admit
+// 12 (3 waves a SIMD).  998,001 points, columns only: 23.2 ms with 4, 15.7 ms with 8, 13.5 ms with 16 (that is 12)
+// (profiles/isovist_points.jsonl).  Hook: DMX_ISO_PWAVES.
+constexpr int kIsoPointsWavesPerCu = 16;
+// launch order of the points: by Morton code of the point over the region (1), so that a wave's 64 lanes walk
+// similar paths through the tree, or the caller's order (0).  Results do not depend on it.  998,001 points in a
+// random order: 110 ms in the caller's order, 13.5 ms in Morton order; in tile order 13.5 and 13.7 ms
+// (profiles/isovist_points.jsonl).  Hook: DMX_ISO_ORDER (caller | morton).
+constexpr int kIsoPointsMorton = 1;
 
 // ---- memory: optional summaries are built only within a share of the free device memory, so a graph
 // that fills the GPU still runs (on the slower exact path that needs no summary)

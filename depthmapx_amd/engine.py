@@ -9,6 +9,7 @@
 Column orders follow the reference attribute tables (see VGA_COLUMNS / MAKEGRAPH_COLUMNS).
 """
 import ctypes
+import math
 
 import numpy as np
 
@@ -27,6 +28,49 @@ VGA_ANGULAR_COLUMNS = ["Angular Mean Depth", "Angular Total Depth", "Angular Nod
 VGA_COLUMNS = ["Visual Entropy", "Visual Integration [HH]", "Visual Integration [P-value]",
                "Visual Integration [Tekl]", "Visual Mean Depth", "Visual Node Count",
                "Visual Relativised Entropy"]
+
+
+def isovist_cone(angle, viewangle, degrees=False):
+    """(startangle, endangle) of a view cone as depthmapXcli -m ISOVIST -ii x,y,angle,viewangle passes them to
+    MetaGraph::makeIsovist: IsovistDefinition::getLeftAngle / getRightAngle (salalib/isovistdef.h:23-54), radians
+    anti-clockwise from the x axis.  A view angle of at least 2 pi means the full circle, (0, 0).  degrees=True
+    converts as EntityParsing::parseIsovist does (salalib/entityparsing.cpp:299-300)."""
+    angle, viewangle = float(angle), float(viewangle)
+    if degrees:
+        angle = angle / 180.0 * math.pi
+        viewangle = viewangle / 180.0 * math.pi
+    if viewangle >= 2 * math.pi:
+        angle = viewangle = 0.0
+    left = angle - 0.5 * viewangle
+    if left < 0:
+        left += 2 * math.pi
+    right = angle + 0.5 * viewangle
+    if right > 2 * math.pi:
+        right -= 2 * math.pi
+    return left, right
+
+
+def isovist_path_cones(polyline, fov):
+    """The isovists MetaGraph::makeIsovistPath makes along a path (mgraph.cpp:523-535, :587-614): for each segment
+    its start point and startendangle(segment vector, fov); fov >= 2 pi gives full circles, (0, 0).  Returns
+    (points float64 [m][2], angles float64 [m][2]) for the m = len(polyline) - 1 segments."""
+    p = np.asarray(polyline, dtype=np.float64).reshape(-1, 2)
+    fov = float(fov)
+    pts = np.ascontiguousarray(p[:-1])
+    ang = np.zeros((len(pts), 2), dtype=np.float64)
+    if fov < 2.0 * math.pi:
+        for i in range(len(pts)):
+            vx, vy = float(p[i + 1, 0] - p[i, 0]), float(p[i + 1, 1] - p[i, 1])
+            s = 1.0 / math.sqrt(vx * vx + vy * vy)   # Point2f::normalise, then Point2f::angle
+            vx, vy = vx * s, vy * s
+            a = (2.0 * math.pi - math.acos(vx)) if vy < 0 else math.acos(vx)
+            first, second = a - fov / 2.0, a + fov / 2.0
+            if first < 0.0:
+                first += 2.0 * math.pi
+            if second > 2.0 * math.pi:
+                second -= 2.0 * math.pi
+            ang[i] = (first, second)
+    return pts, ang
 
 
 class Context:
@@ -87,13 +131,50 @@ class Context:
                     improved=int(d[2]), ambiguous=int(d[3]))
 
     def last_isovist(self):
-        """The last Graph.vga_isovist (dmx_ctx_last_isovist): seconds of the host BSP build and of the kernels,
-        the tree's nodes and depth, the cells run again for capacity and the most blocks any cell held."""
+        """The last Graph.vga_isovist or Context.isovists (dmx_ctx_last_isovist): seconds of the host BSP build and
+        of the kernels, the tree's nodes and depth, the cells (points) run again for capacity and the most blocks
+        any of them held."""
         b, k = ctypes.c_double(), ctypes.c_double()
         d = np.zeros(4, dtype=np.int64)
         N.check(N.lib().dmx_ctx_last_isovist(self.h, ctypes.byref(b), ctypes.byref(k), N.ptr(d)))
         return dict(bsp_seconds=b.value, kernel_seconds=k.value, tree_nodes=int(d[0]), tree_depth=int(d[1]),
                     reruns=int(d[2]), max_blocks=int(d[3]))
+
+    ISOVIST_POLY_GUESS = 128   # vertices a point the first call with polygons=True makes room for
+
+    def isovists(self, lines, points, angles=None, region=None, simple=False, polygons=False):
+        """A batch of isovists at arbitrary points of a drawing, on the GPU (dmx_isovists; MetaGraph::makeIsovist,
+        mgraph.cpp:491-521, per point).  lines [m][4], points [n][2]; angles [n][2] (startangle, endangle) in
+        radians as Isovist::makeit takes them -- see isovist_cone / isovist_path_cones -- or None for full circles;
+        region [4] the drawing's region (None: the bounding box of lines).  Returns out float32 [n][8] in the order
+        of Graph.ISOVIST_COLUMNS (rows start at -1; simple=True writes column 0 only), and with polygons=True
+        (out, off int64 [n + 1], xy float64 [total][2]): the polygons' vertices as a CSR in the order of points.
+        With polygons the call is made once with room for ISOVIST_POLY_GUESS vertices a point, and a second time
+        only when there were more."""
+        lines = np.ascontiguousarray(lines, dtype=np.float64).reshape(-1, 4)
+        points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+        n = len(points)
+        if angles is not None:
+            angles = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1, 2)
+            assert len(angles) == n
+        if region is not None:
+            region = np.ascontiguousarray(region, dtype=np.float64).reshape(4)
+        out = np.full((n, 8), -1.0, dtype=np.float32)
+        lib = N.lib()
+        args = (self.h, N.ptr(lines), len(lines), N.ptr(region), N.ptr(points), N.ptr(angles), n, int(bool(simple)),
+                N.ptr(out))
+        if not polygons:
+            N.check(lib.dmx_isovists(*args, None, None, 0, None))
+            return out
+        off = np.zeros(n + 1, dtype=np.int64)
+        total = ctypes.c_int64()
+        xy = np.empty((max(self.ISOVIST_POLY_GUESS * n, 1), 2), dtype=np.float64)
+        for _ in range(2):
+            N.check(lib.dmx_isovists(*args, N.ptr(off), N.ptr(xy), len(xy), ctypes.byref(total)))
+            if total.value <= len(xy):
+                break
+            xy = np.empty((total.value, 2), dtype=np.float64)
+        return out, off, xy[:total.value]
 
     def last_mk_reruns(self):
         """The sources the last makeGraph swept again: (certificate re-runs, capacity re-runs), node indices

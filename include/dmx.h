@@ -283,9 +283,37 @@ int dmx_vga_isovist(dmx_ctx* ctx, dmx_graph* g, int simple_version, int64_t src_
                     float* out /* host [N][8] */, float* occ_dist /* host [N][32], optional */,
                     int32_t* occ_counts /* host [N][32], optional */, int32_t* occ_pixels, int64_t occ_cap,
                     int64_t* occ_total);
-/* The last dmx_vga_isovist: seconds of the host BSP build and of the kernels (either may be NULL), and out4 =
- * tree nodes, tree depth, cells run again for capacity, the most blocks a cell held. */
+/* The last dmx_vga_isovist or dmx_isovists: seconds of the host BSP build and of the kernels (either may be NULL),
+ * and out4 = tree nodes, tree depth, cells (points) run again for capacity, the most blocks a cell (point) held. */
 int dmx_ctx_last_isovist(dmx_ctx* ctx, double* bsp_s, double* kernel_s, int64_t* out4);
+/* ---- Isovists at arbitrary points (GPU) -------------------------------------------------------- */
+/* MetaGraph::makeIsovist (salalib/mgraph.cpp:491-521; depthmapXcli -m ISOVIST, runmethods.cpp:635-647) for a batch of
+ * n points: Isovist::makeit(root, p, region, startangle, endangle) and setData (salalib/isovist.cpp:31-120, :270-335)
+ * per point, from the drawing alone -- no point map and no graph.  A BSP tree of `lines` ([nlines][4] = x1,y1,x2,y2)
+ * is built on the host.
+ *   region   [4] blx, bly, trx, try: what makeit takes for its tolerance (MetaGraph::m_region, the drawing's bounding
+ *            box; tolerance = max(width, height) * 1e-9).  NULL: the bounding box of lines.
+ *   points   [n][2].  angles [n][2] startangle, endangle in radians as makeit takes them (start == end or (0, 2 pi):
+ *            full circle; start > end: a cone across angle 0), or NULL: full circles.
+ *   out      host [n][8], columns in the table order of dmx_vga_isovist; simple_version: only column 0 of a row is
+ *            written.
+ *   poly_off / poly_xy   optional CSR in the caller's order: poly_off [n + 1], poly_xy [poly_cap][2] the polygons'
+ *            vertices (Isovist::getPolygon(), m_poly order, in doubles; a cone's polygon holds its centre).
+ *            *poly_total (optional) receives their number; poly_xy NULL or poly_cap < *poly_total: poly_off and
+ *            *poly_total are set and no vertex is written (DMX_OK).  Where the tree cuts a wall the polygon holds a
+ *            vertex on that wall, as the reference's does; the reference's cuts depend on the state of its random
+ *            generator (BSPTree::makeLines), so vertex counts agree with it only after dropping those collinear
+ *            vertices.
+ * n == 0: DMX_OK.  No (or only zero-length) lines: DMX_ERR_STATE.  A coordinate or angle that is not finite:
+ * DMX_ERR_ARG.  Per-point lists have the capacities of dmx_vga_isovist; a point that exceeds one is run again with
+ * larger lists, DMX_ERR_CAPACITY only after that.  Progress and cancel as in dmx_vga_isovist (phase DMX_PHASE_VGA; the
+ * unit is 64 points).  On an error or a cancel no output array is touched.  Results do not depend on the order of
+ * the points. */
+int dmx_isovists(dmx_ctx* ctx, const double* lines, int64_t nlines, const double* region /* [4] or NULL */,
+                 const double* points /* [n][2] */, const double* angles /* [n][2] start,end or NULL: full circle */,
+                 int64_t n, int simple_version, float* out /* [n][8] */,
+                 int64_t* poly_off /* [n+1] or NULL */, double* poly_xy /* [poly_cap][2] or NULL */,
+                 int64_t poly_cap, int64_t* poly_total /* or NULL */);
 /* Multi-GPU share of the VGA preparation (no reference counterpart: the reference prepares nothing;
  * this splits our own O(runs) pre-passes).  Every rank holds the whole graph; the per-node scatters
  * (in-set hash sums, tile-visibility rows) then run over nodes [node_begin, node_end)

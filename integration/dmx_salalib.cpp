@@ -18,6 +18,7 @@
 #include "dmx.h"
 #include "genlib/comm.h"
 #include "genlib/exceptions.h"
+#include "salalib/mgraph.h"
 #include "salalib/pointdata.h"
 
 namespace dmxsala {
@@ -27,6 +28,10 @@ namespace {
 // name the member, and the pointer-to-member then reads it from any PointMap.
 struct RegionAccess : PointMap {
     static const QtRegion* parent(const PointMap& m) { return m.*(&RegionAccess::m_parentRegion); }
+};
+// the same for MetaGraph::m_view_class, which makeIsovist clears VIEWDATA in
+struct ViewAccess : MetaGraph {
+    static int& view_class(MetaGraph& m) { return m.*(&ViewAccess::m_view_class); }
 };
 
 void check(int status) {
@@ -342,6 +347,87 @@ bool vgaIsovist(PointMap& map, Communicator* comm, bool simple_version) {
     if (!load(map, serialize(c.p))) return false;
     map.m_hasIsovistAnalysis = true;
     return true;
+}
+
+// MetaGraph::makeIsovist (mgraph.cpp:491-521) for a batch of points: one dmx_isovists call makes the polygons and
+// the attribute values; each polygon then enters the "Isovists" data map through the reference's own
+// makePolyShape / setCentroid, and its row gets the columns in the order Isovist::setData inserts them
+// (isovist.cpp:308-332).  The drawing lines are those makeBSPtree partitions (mgraph.cpp:643-664).
+int makeIsovists(MetaGraph& mg, const std::vector<Point2f>& points, const std::vector<std::pair<double, double>>& angles,
+                 bool simple_version) {
+    dmx_ctx* ctx = context();
+    if (!ctx || (!angles.empty() && angles.size() != points.size())) return 0;
+    std::vector<double> lines;
+    for (const auto& file : mg.m_drawingFiles)
+        for (const auto& layer : file.m_spacePixels)
+            if (layer.isShown())
+                for (const auto& shape : layer.getAllShapes())
+                    for (const Line& l : shape.second.getAsLines())
+                        if (l.length() > 0.0) {
+                            lines.push_back(l.start().x);
+                            lines.push_back(l.start().y);
+                            lines.push_back(l.end().x);
+                            lines.push_back(l.end().y);
+                        }
+    if (lines.empty()) return 0;   // makeBSPtree fails: no isovist is made
+    const int64_t n = (int64_t)points.size();
+    const QtRegion& r = mg.getRegion();
+    const double region[4] = {r.bottom_left.x, r.bottom_left.y, r.top_right.x, r.top_right.y};
+    std::vector<double> pts((size_t)n * 2), ang((size_t)n * 2, 0.0);
+    for (int64_t k = 0; k < n; k++) {
+        pts[2 * k] = points[k].x;
+        pts[2 * k + 1] = points[k].y;
+        if (!angles.empty()) {
+            ang[2 * k] = angles[k].first;
+            ang[2 * k + 1] = angles[k].second;
+        }
+    }
+    std::vector<float> out((size_t)n * 8, -1.0f);
+    std::vector<int64_t> off((size_t)n + 1, 0);
+    std::vector<double> xy;
+    int64_t total = 0;
+    check(dmx_isovists(ctx, lines.data(), (int64_t)lines.size() / 4, region, pts.data(), ang.data(), n, simple_version ? 1 : 0,
+                       out.data(), off.data(), nullptr, 0, &total));
+    xy.resize((size_t)std::max<int64_t>(total, 1) * 2);
+    check(dmx_isovists(ctx, lines.data(), (int64_t)lines.size() / 4, region, pts.data(), ang.data(), n, simple_version ? 1 : 0,
+                       out.data(), off.data(), xy.data(), total, &total));
+    if (n == 0) return 1;
+    int made = 1;
+    ViewAccess::view_class(mg) &= ~MetaGraph::VIEWDATA;
+    std::vector<ShapeMap>& maps = mg.getDataMaps();
+    int shapelayer = -1;
+    for (size_t i = 0; i < maps.size(); i++)
+        if (maps[i].getName() == "Isovists") shapelayer = (int)i;
+    if (shapelayer == -1) {
+        maps.emplace_back("Isovists", ShapeMap::DATAMAP);
+        mg.setDisplayedDataMapRef(maps.size() - 1);
+        shapelayer = (int)maps.size() - 1;
+        mg.setState(mg.getState() | MetaGraph::DATAMAPS);
+        made = 2;
+    }
+    ShapeMap& map = maps[(size_t)shapelayer];
+    // the columns in the order setData inserts them; none of them exists before the first isovist
+    static const struct { const char* name; int k; } cols[8] = {
+        {"Isovist Area", 0}, {"Isovist Compactness", 1}, {"Isovist Drift Angle", 2}, {"Isovist Drift Magnitude", 3},
+        {"Isovist Min Radial", 5}, {"Isovist Max Radial", 4}, {"Isovist Occlusivity", 6}, {"Isovist Perimeter", 7}};
+    std::vector<Point2f> poly;
+    for (int64_t k = 0; k < n; k++) {
+        poly.clear();
+        for (int64_t v = off[(size_t)k]; v < off[(size_t)k + 1]; v++) poly.push_back(Point2f(xy[2 * v], xy[2 * v + 1]));
+        const int polyref = map.makePolyShape(poly, false);   // false: closed polygon
+        if (polyref == -1) continue;                          // an empty polygon makes no shape
+        map.getAllShapes()[polyref].setCentroid(points[k]);
+        AttributeTable& table = map.getAttributeTable();
+        AttributeRow& row = table.getRow(AttributeKey(polyref));
+        for (const auto& col : cols) {
+            if (simple_version && col.k != 0) continue;
+            row.setValue(table.getOrInsertColumn(col.name), out[(size_t)k * 8 + col.k]);
+        }
+    }
+    map.overrideDisplayedAttribute(-2);
+    map.setDisplayedAttribute(-1);
+    mg.setViewClass(MetaGraph::SHOWSHAPETOP);
+    return made;
 }
 
 }  // namespace dmxsala

@@ -15,7 +15,12 @@
 // depthmapX::RuntimeException.
 #pragma once
 
+#include <utility>
+#include <vector>
+
 class Communicator;
+class MetaGraph;
+class Point2f;
 class PointMap;
 
 namespace dmxsala {
@@ -29,6 +34,15 @@ bool vgaThroughVision(PointMap& map, Communicator* comm);
 // and occ distances, m_hasIsovistAnalysis; false also for a map without drawing lines or one that already has
 // "Isovist Area".  Values agree with the reference within 1e-6 relative (the platform's acos / sin / cos).
 bool vgaIsovist(PointMap& map, Communicator* comm, bool simple_version);
+
+// MetaGraph::makeIsovist (salalib/mgraph.cpp:491-521) for a batch of points, what depthmapXcli -m ISOVIST loops over
+// (runmethods.cpp:635-647): the polygons and attribute values come from one dmx_isovists call, the "Isovists" data
+// map from the reference's own ShapeMap::makePolyShape / setCentroid and AttributeRow::setValue.  angles: (startangle,
+// endangle) per point as makeIsovist takes them, or empty for full circles.  Returns what makeIsovist returns: 0
+// nothing made (no GPU, no drawing lines: the caller runs its own loop), 1 isovists made, 2 and the data map added.
+// Polygon vertices on a wall the BSP tree cuts depend on the tree, as they do in the reference (include/dmx.h).
+int makeIsovists(MetaGraph& mg, const std::vector<Point2f>& points, const std::vector<std::pair<double, double>>& angles,
+                 bool simple_version);
 
 // Test hooks (integration/bind_check.cpp): the PointMap <-> PointMap::write image conversions the two
 // calls are built on.
