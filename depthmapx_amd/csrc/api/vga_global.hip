@@ -836,7 +836,8 @@ static int vga_tile_impl(dmx_ctx* ctx, dmx_graph* g, double radius, int gates_on
     ctx->last_stats[9] = (long long)st[6];
     ctx->last_stats[10] = 0;
     ctx->last_stats[11] = (long long)st[7];
-    ctx->last_stats[12] = blocks | ((long long)kt << 32) | ((long long)ntpb << 40) | ((long long)fg << 56);
+    ctx->last_stats[12] = blocks | ((long long)kt << 32) | ((long long)ntpb << 40) | ((long long)fg << 56) |
+                          ((long long)rbm << 57);
     ctx->last_stats[13] = (long long)st[13];
     ctx->last_stats[14] = (long long)st[14] * g->tvw * 8;   // bytes of tile-visibility rows read
     ctx->last_stats[15] = (long long)st[15];                          // runs scanned in phase C

@@ -210,7 +210,9 @@ class Context:
         d["vga_bottom_up_levels"], d["vga_top_down_levels"] = lv & 0xFFFFFFFF, lv >> 32
         d["vga_special_nodes"] = d["vga_kernel"] >> 8
         d["vga_frontier_hbm"] = (d["vga_launch"] >> 56) & 1   # tile BFS with its frontier in HBM (grids > 1024^2)
-        d["vga_launch"] &= (1 << 56) - 1
+        d["vga_line_summaries"] = (d["vga_launch"] >> 57) & 1   # ... with line summaries (else per-tile ones)
+        d["vga_threads"] = (d["vga_launch"] >> 40) & 0xFFFF   # ... threads a workgroup (256 or 1024)
+        d["vga_launch"] &= (1 << 32) - 1   # its workgroups
         f = d["vga_prep_flags"]   # the memory-dependent preparation the last VGA search ran with
         d["vga_scan_order"], d["vga_scan_released"] = f & 1, (f >> 1) & 1
         d["vga_prep"] = "+".join(n for b, n in enumerate(["scan", "scan-released", "tvis", "ftvis", "ttvis", "masks",

@@ -80,7 +80,8 @@ int dmx_ctx_last_timing(dmx_ctx* ctx, double* makegraph_s, double* vga_s);
  * [4] runs read by the BFS, [5] bottom-up levels | top-down levels << 32, [6] cells reached (sum
  * over sources), [7] sources run, [8] bottom-up cells that found no hit, [9] their runs,
  * [10] bitmaps in HBM (direction-optimising), [11] tiles resolved by common runs, [12] launch
- * shape, [13] hard cells rejected by their tile-visibility row, [14] bytes of those rows read,
+ * shape of the tile-resolved search (workgroups | threads a workgroup (256 or 1024) << 40 | frontier bitmap in
+ * HBM << 56 | line-resolved summaries (else per-tile column summaries) << 57), [13] hard cells rejected by their tile-visibility row, [14] bytes of those rows read,
  * [15] runs scanned by hard cells, [16] hard cells that hit, [17] hard cells, ... [38] searches the last VGA
  * global / visual step depth call ran again in the reference's level order (vga_ordered.hip), [39] microseconds
  * the last VGA preparation spent on the symmetry scatter and its all-reduces (0 when makeGraph did it), [40] the

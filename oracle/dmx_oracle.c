@@ -1745,6 +1745,12 @@ int dmxo_vga_local(dmxo_map* m, int gates_only, int64_t nb, int64_t ne, int nthr
  * be set: dmxo_set_graph), its wall time in secs[i]; out [N][7] rows of the sample. */
 int dmxo_vga_global_sample(dmxo_map* m, double radius, const int64_t* nodes, int64_t n, int nthreads, float* out,
                            double* secs) {
+    return dmxo_vga_global_sample_lv(m, radius, nodes, n, nthreads, out, secs, NULL);
+}
+
+/* ... and, with lv != NULL, the sample's rows of dmxo_vga_global's lv [N][3] (nodes, total depth, levels). */
+int dmxo_vga_global_sample_lv(dmxo_map* m, double radius, const int64_t* nodes, int64_t n, int nthreads, float* out,
+                              double* secs, int64_t* lv) {
     for (int64_t i = 0; i < n; i++)
         if (nodes[i] < 0 || nodes[i] >= m->nnodes) return -1;
 #ifdef _OPENMP
@@ -1753,7 +1759,7 @@ int dmxo_vga_global_sample(dmxo_map* m, double radius, const int64_t* nodes, int
 #endif
     for (int64_t i = 0; i < n; i++) {
         const double t0 = omp_get_wtime();
-        dmxo_vga_global(m, radius, 0, nodes[i], nodes[i] + 1, 1, out, NULL);
+        dmxo_vga_global(m, radius, 0, nodes[i], nodes[i] + 1, 1, out, lv);
         secs[i] = omp_get_wtime() - t0;
     }
     return 0;

@@ -106,6 +106,8 @@ void dmxo_get_graph_range(const dmxo_map* m, int64_t nb, int64_t ne, float* attr
 void dmxo_release_range(dmxo_map* m, int64_t nb, int64_t ne);
 int dmxo_vga_global_sample(dmxo_map* m, double radius, const int64_t* nodes, int64_t n, int nthreads, float* out,
                            double* secs);
+int dmxo_vga_global_sample_lv(dmxo_map* m, double radius, const int64_t* nodes, int64_t n, int nthreads, float* out,
+                              double* secs, int64_t* lv);
 
 #ifdef __cplusplus
 }

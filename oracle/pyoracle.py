@@ -68,6 +68,8 @@ def lib():
         L.dmxo_makegraph_sample.argtypes = [vp, dbl, vp, i64, i32, vp]
         L.dmxo_vga_global_sample.restype = i32
         L.dmxo_vga_global_sample.argtypes = [vp, dbl, vp, i64, i32, vp, vp]
+        L.dmxo_vga_global_sample_lv.restype = i32
+        L.dmxo_vga_global_sample_lv.argtypes = [vp, dbl, vp, i64, i32, vp, vp, vp]
         L.dmxo_create_grid.restype = vp
         L.dmxo_create_grid.argtypes = [i32, i32, dbl, dbl, dbl]
         L.dmxo_set_state.restype = None
@@ -269,14 +271,17 @@ class OracleMap:
             raise ValueError("node out of range")
         return secs
 
-    def vga_global_sample(self, nodes, radius=-1.0, threads=1):
-        """VGA global BFS from each listed source (one source per thread): ([N][7] rows, per-source seconds)."""
+    def vga_global_sample(self, nodes, radius=-1.0, threads=1, levels=False):
+        """VGA global BFS from each listed source (one source per thread): ([N][7] rows, per-source seconds), and
+        with levels=True vga_global's [N][3] level rows as a third item."""
         nodes = np.ascontiguousarray(nodes, dtype=np.int64)
         out = np.full((self.num_nodes, 7), -1.0, dtype=np.float32)
         secs = np.zeros(len(nodes))
-        if lib().dmxo_vga_global_sample(self.h, float(radius), _p(nodes), len(nodes), int(threads), _p(out), _p(secs)):
+        lv = np.zeros((self.num_nodes, 3), dtype=np.int64) if levels else None
+        if lib().dmxo_vga_global_sample_lv(self.h, float(radius), _p(nodes), len(nodes), int(threads), _p(out), _p(secs),
+                                           _p(lv) if levels else None):
             raise ValueError("node out of range")
-        return out, secs
+        return (out, secs, lv) if levels else (out, secs)
 
 
 def set_pop_forward(forward):

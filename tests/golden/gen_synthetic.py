@@ -27,16 +27,38 @@ def make_lines(W, n, seed=1, lmin=0.02, lmax=0.10):
     return lines
 
 
-def make_room_map(W, room, nocc, seed):
-    """A W x W region with a walled room of side `room` near the middle and `nocc` occluders in it: the grid is
-    the whole region's while the filled cells (and the cost of a CPU graph) are the room's.  Returns (region,
-    lines [n][4], seed point inside the room)."""
+def make_lines_rect(W, H, n, seed=1, lmin=0.02, lmax=0.10):
+    """make_lines on a W x H region: centres uniform in [0.05W, 0.95W] x [0.05H, 0.95H], lengths uniform in
+    [lmin, lmax] * min(W, H)."""
+    rng = np.random.default_rng(seed)
+    W, H = float(W), float(H)
+    S = min(W, H)
+    lines = [(0.0, 0.0, W, 0.0), (W, 0.0, W, H), (W, H, 0.0, H), (0.0, H, 0.0, 0.0)]
+    for _ in range(n):
+        cx = rng.uniform(0.05 * W, 0.95 * W)
+        cy = rng.uniform(0.05 * H, 0.95 * H)
+        a = rng.uniform(0.0, math.pi)
+        half = 0.5 * rng.uniform(lmin * S, lmax * S)
+        dx, dy = half * math.cos(a), half * math.sin(a)
+        lines.append((cx - dx, cy - dy, cx + dx, cy + dy))
+    return lines
+
+
+def make_room_map(W, room, nocc, seed, centre=None):
+    """A W x W region with a walled room of side `room` around `centre` (default: the middle) and `nocc` occluders
+    in it: the grid is the whole region's while the filled cells (and the cost of a CPU graph) are the room's.
+    The occluders keep their place in the room wherever it stands.  Returns (region, lines [n][4], seed point
+    inside the room)."""
     rng = np.random.default_rng(seed)
     x0 = y0 = W / 2 - room / 2
-    x1 = y1 = x0 + room
+    if centre is not None:
+        x0, y0 = centre[0] - room / 2, centre[1] - room / 2
+    x1, y1 = x0 + room, y0 + room
+    assert 0 < x0 and x1 < W and 0 < y0 and y1 < W, "room outside the region"
     walls = [[0, 0, W, 0], [W, 0, W, W], [W, W, 0, W], [0, W, 0, 0],
              [x0, y0, x1, y0], [x1, y0, x1, y1], [x1, y1, x0, y1], [x0, y1, x0, y0]]
     c = rng.uniform(x0 + 2, x1 - 2, size=(nocc, 2))
+    c[:, 1] += y0 - x0
     ang = rng.uniform(0, np.pi, size=nocc)
     ln = rng.uniform(1.0, room / 6, size=nocc)
     d = np.stack([np.cos(ang), np.sin(ang)], 1) * (ln / 2)[:, None]
@@ -44,6 +66,26 @@ def make_room_map(W, room, nocc, seed):
     region = [0.0, 0.0, float(W), float(W)]
     seed_pt = (x0 + 1.3, y0 + 1.3)
     return region, lines, seed_pt
+
+
+def make_strip_map(W, H, parts, nocc, seed):
+    """A W x H strip: a closed border, `parts` partitions across the short side at even steps along the long one,
+    alternately from one long wall and the other and each leaving a gap of 38 % of the short side (a search
+    from one end is about `parts` levels deep), and `nocc` seeded occluders shorter than a cell.  Returns
+    (region, lines [4 + parts + nocc][4], fill point)."""
+    rng = np.random.default_rng(seed)
+    W, H = float(W), float(H)
+    walls = [[0, 0, W, 0], [W, 0, W, H], [W, H, 0, H], [0, H, 0, 0]]
+    long_x = W > H
+    L, S = max(W, H), min(W, H)
+    for i, t in enumerate(np.linspace(L / (parts + 1), L * parts / (parts + 1), parts)):
+        a, b = (0.0, S * 0.62) if i % 2 else (S * 0.38, S)
+        walls.append([t + 0.37, a, t + 0.37, b] if long_x else [a, t + 0.37, b, t + 0.37])
+    for _ in range(nocc):
+        x = rng.uniform(1, W - 1)
+        y = rng.uniform(1, H - 1)
+        walls.append([x, y, x + rng.uniform(-.6, .6), y + rng.uniform(-.6, .6)])
+    return [0.0, 0.0, W, H], np.array(walls, dtype=np.float64), (0.5, 0.5)
 
 
 # Small walled rooms on grids whose world coordinates are not exact in FP64 (name: origin, spacing, cells a

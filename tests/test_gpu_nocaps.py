@@ -94,7 +94,8 @@ def test_visual_stepdepth_topdown_equals_tile(ctx, monkeypatch, seed):
 
 
 def test_visual_stepdepth_above_1024_matches_oracle(ctx):
-    """1100^2 cells (19,044 tiles, past the tile BFS's 16,384): top-down vs the restatement."""
+    """1100^2 cells (19,044 tiles: visual step depth takes the tile BFS in seed mode up to 16,384, api/stepdepth.hip):
+    the top-down search vs the restatement."""
     from pyoracle import OracleMap
     region, lines, sp = _room_map(1100.0, 64.0, 60, seed=9)
     pm = dmx.PointMap(region, lines, 1.0)
@@ -114,8 +115,10 @@ def test_visual_stepdepth_above_1024_matches_oracle(ctx):
 
 
 def test_vga_source_list_above_1024_matches_full_run(ctx):
-    """dmx_vga_global_device_list past the tile BFS (1100^2): runs of consecutive listed nodes go
-    through the direction-optimising kernel; listed rows equal the full run's, the others are
+    """dmx_vga_global_device_list at 1100^2 (19,044 tiles).  VGA global has no tile cap there: the full run and the
+    source list both take the tile-resolved search, 1024 threads with the frontier (152 KB) still in the LDS, per-tile
+    summaries instead of the line summaries, wide tile-visibility rows with their summaries and none of the other
+    certificates (tests/test_gpu_vga_variants.py case E).  Listed rows equal the full run's, the others are
     untouched, and a block of them equals the restatement's BFS."""
     import torch
     from pyoracle import OracleMap
@@ -128,8 +131,12 @@ def test_vga_source_list_above_1024_matches_full_run(ctx):
     rng = np.random.default_rng(3)
     nodes = np.unique(np.concatenate([rng.choice(n, n // 4, replace=False), np.arange(100, 164)]))
     out = torch.full((n, 7), -7.0, dtype=torch.float32, device="cuda")
+    variant = lambda st: (st["vga_kernel"], st["vga_threads"], st["vga_frontier_hbm"], st["vga_line_summaries"], st["vga_prep"])
+    want_variant = ("tile-resolved", 1024, 0, 0, "scan+tvis+tvsum")
+    assert variant(ctx.last_stats()) == want_variant and ctx.last_stats()["vga_sources"] == n
     g.vga_visual_global_device_list(out.data_ptr(), nodes)
     torch.cuda.synchronize()
+    assert variant(ctx.last_stats()) == want_variant and ctx.last_stats()["vga_sources"] == len(nodes)
     got = out.cpu().numpy()
     np.testing.assert_array_equal(got[nodes].view(np.uint32), full[nodes].view(np.uint32))
     assert (got[np.setdiff1d(np.arange(n), nodes)] == -7.0).all()
