@@ -88,6 +88,9 @@ SIGNATURES = {
     "dmx_chunk_select_cells": (_i32, [_vp, _vp, _i64]),
     "dmx_chunk_unmake": (_i32, [_vp, _i32]),
     "dmx_chunk_serialize": (_i32, [_vp, _vp, _i64, _vp]),
+    "dmx_graph_chunk_write": (_i32, [_vp, _cs, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),
+    "dmx_chunk_scan": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "dmx_chunk_load_bytes": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "dmx_graphfile_read": (_i32, [_cs, _vp]),
     "dmx_graphfile_free": (_i32, [_vp]),
     "dmx_graphfile_write": (_i32, [_vp, _cs]),

@@ -64,11 +64,9 @@ int dmx_graph_from_runs(dmx_ctx* ctx, dmx_pointmap* pm, int64_t nnodes, const in
     return DMX_OK;
 }
 
-int dmx_chunk_write(const dmx_pointmap* pm, int64_t nnodes, const int32_t* bins, const int16_t* runs, int64_t nruns,
-                    const uint8_t* gridconn, int ncols, const char* const* names, const float* values,
-                    const uint8_t* locked, const uint8_t* setmask, int displayed, int boundary, uint8_t* buf, int64_t cap,
-                    int64_t* size) {
-    if (!pm || !size || nnodes < 0 || ncols < 0 || (ncols && (!names || !values))) return fail(DMX_ERR_ARG, "bad arguments");
+// the columns of dmx_chunk_write / dmx_graph_chunk_write: values and setmask [ncols][nnodes], insertion order
+static std::vector<ChunkColumn> chunk_columns(int64_t nnodes, int ncols, const char* const* names, const float* values,
+                                              const uint8_t* locked, const uint8_t* setmask) {
     std::vector<ChunkColumn> cols((size_t)ncols);
     for (int i = 0; i < ncols; i++) {
         cols[i].name = names[i];
@@ -76,6 +74,15 @@ int dmx_chunk_write(const dmx_pointmap* pm, int64_t nnodes, const int32_t* bins,
         cols[i].values.assign(values + (size_t)i * nnodes, values + (size_t)(i + 1) * nnodes);
         if (setmask) cols[i].set.assign(setmask + (size_t)i * nnodes, setmask + (size_t)(i + 1) * nnodes);
     }
+    return cols;
+}
+
+int dmx_chunk_write(const dmx_pointmap* pm, int64_t nnodes, const int32_t* bins, const int16_t* runs, int64_t nruns,
+                    const uint8_t* gridconn, int ncols, const char* const* names, const float* values,
+                    const uint8_t* locked, const uint8_t* setmask, int displayed, int boundary, uint8_t* buf, int64_t cap,
+                    int64_t* size) {
+    if (!pm || !size || nnodes < 0 || ncols < 0 || (ncols && (!names || !values))) return fail(DMX_ERR_ARG, "bad arguments");
+    const std::vector<ChunkColumn> cols = chunk_columns(nnodes, ncols, names, values, locked, setmask);
     std::vector<uint8_t> out;
     std::string err;
     if (write_pointmap_chunk(*pm->host, nnodes, bins, runs, nruns, gridconn, cols, displayed, boundary != 0, out, err))
@@ -299,6 +306,240 @@ int dmx_chunk_unmake(dmx_chunk* c, int remove_links) {
     if (!c) return fail(DMX_ERR_ARG, "chunk is NULL");
     std::string err;
     if (chunk_unmake(c->pc, remove_links != 0, err)) return fail(DMX_ERR_STATE, err);
+    return DMX_OK;
+}
+
+// ---------------------------------------------------------------- the chunk's records on the GPU (chunk_codec.hip)
+// Two slabs of the record stream in device memory and two in pinned host memory, with the events that order them.
+struct CodecStage {
+    DevBuf<uint8_t> dev[2];
+    uint8_t* pin[2] = {nullptr, nullptr};
+    hipEvent_t done[2] = {nullptr, nullptr};     // the slab's last operation (its copy)
+    hipEvent_t kernel[2] = {nullptr, nullptr};   // encode: the slab's kernels
+    ~CodecStage() {
+        for (int i = 0; i < 2; i++) {
+            if (pin[i]) (void)hipHostFree(pin[i]);
+            if (done[i]) (void)hipEventDestroy(done[i]);
+            if (kernel[i]) (void)hipEventDestroy(kernel[i]);
+        }
+    }
+    hipError_t init(size_t bytes, int nbuf) {
+        for (int i = 0; i < nbuf; i++) {
+            hipError_t e = dev[i].alloc(bytes);
+            if (e == hipSuccess) e = hipHostMalloc((void**)&pin[i], std::max<size_t>(bytes, 1), hipHostMallocDefault);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&done[i], hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&kernel[i], hipEventDisableTiming);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+};
+
+static int64_t codec_slab_bytes() {
+    const int64_t s = policy::hook_int("DMX_CODEC_SLAB", 0);
+    return s > 0 ? s : policy::kCodecSlabBytes;
+}
+
+int dmx_graph_chunk_write(dmx_graph* g, const char* map_name, int ncols, const char* const* names, const float* values,
+                          const uint8_t* locked, const uint8_t* setmask, int displayed, int boundary, uint8_t* buf,
+                          int64_t cap, int64_t* size) {
+    if (!g || !size || ncols < 0 || (ncols && (!names || !values))) return fail(DMX_ERR_ARG, "bad arguments");
+    if (g->node_begin != 0 || g->node_end != g->nnodes)
+        return fail(DMX_ERR_STATE, "a shard of a graph cannot be written as a chunk (assemble the whole graph first)");
+    dmx_ctx* ctx = g->ctx;
+    const PointMapHost& h = *g->pm->host;
+    const int64_t N = g->nnodes, C = h.cells();
+    // a name of its own: the bytes PointMap::read + ::write give for the renamed map (dmx_chunk_set_name + serialize)
+    const bool named = map_name && std::strcmp(map_name, "VGA Map") != 0;
+    if (named && ncols > 4096) return fail(DMX_ERR_ARG, "not a PointMap chunk");
+    const std::vector<ChunkColumn> cols = chunk_columns(N, ncols, names, values, locked, setmask);
+    std::vector<uint8_t> head, tail;
+    std::string err;
+    if (write_pointmap_head(h, N, true, cols, displayed, named ? map_name : "VGA Map", named, head, err))
+        return fail(DMX_ERR_ARG, err);
+    write_pointmap_tail(true, boundary != 0, tail);
+    // per cell: the state as written, the merge partner, the node
+    std::vector<int32_t> state(h.state()), cell_node((size_t)C, -1);
+    {
+        int32_t k = 0;
+        for (int64_t c = 0; c < C; c++) {
+            if (state[c] & CELL_FILLED) cell_node[c] = k++;
+            if (named) state[c] &= kChunkStateMask;
+        }
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    DevBuf<int32_t> d_state, d_merge, d_cell_node;
+    DevBuf<int64_t> d_sizes, d_offsets, d_tiles;
+    DevBuf<int> d_err;
+    const bool links = !h.merge().empty();
+    const int64_t nt = (C + CC_SCAN_TILE - 1) / CC_SCAN_TILE;
+    HIPCHK(d_state.alloc(C));
+    HIPCHK(d_cell_node.alloc(C));
+    if (links) HIPCHK(d_merge.alloc(C));
+    HIPCHK(d_sizes.alloc(C));
+    HIPCHK(d_offsets.alloc(C + 1));
+    HIPCHK(d_tiles.alloc(nt + 1));
+    HIPCHK(d_err.alloc(1));
+    HIPCHK(hipMemcpyAsync(d_state.p, state.data(), C * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_cell_node.p, cell_node.data(), C * 4, hipMemcpyHostToDevice, s));
+    if (links) HIPCHK(hipMemcpyAsync(d_merge.p, h.merge().data(), C * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(d_err.p, 0, sizeof(int), s));
+    // sizes, then their exclusive scan
+    hipLaunchKernelGGL(cc_size_kernel, dim3((unsigned)((C * 32 + CC_THREADS - 1) / CC_THREADS)), dim3(CC_THREADS), 0, s, C,
+                       d_cell_node.p, g->bin_nruns.p, g->bin_count.p, d_sizes.p, d_err.p);
+    hipLaunchKernelGGL(cc_scan_reduce_kernel, dim3((unsigned)nt), dim3(CC_THREADS), 0, s, d_sizes.p, C, d_tiles.p);
+    hipLaunchKernelGGL(cc_scan_tiles_kernel, dim3(1), dim3(CC_THREADS), 0, s, d_tiles.p, nt);
+    hipLaunchKernelGGL(cc_scan_down_kernel, dim3((unsigned)nt), dim3(CC_THREADS), 0, s, d_sizes.p, C, d_tiles.p, nt,
+                       d_offsets.p);
+    HIPCHK(hipGetLastError());
+    int bad = 0;
+    int64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&bad, d_err.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(copy_sync(s, &total, d_offsets.p + C, 8, hipMemcpyDeviceToHost));
+    if (bad) return fail(DMX_ERR_ARG, "bin with a node count but no runs");
+    *size = (int64_t)head.size() + total + (int64_t)tail.size();
+    if (!buf || cap < *size) return DMX_OK;
+    std::vector<int64_t> off((size_t)C + 1);
+    HIPCHK(copy_sync(s, off.data(), d_offsets.p, (C + 1) * 8, hipMemcpyDeviceToHost));
+    std::memcpy(buf, head.data(), head.size());
+    uint8_t* rec = buf + head.size();
+    // the records, slab by slab: the next slab's kernels run beside the copy of this one
+    if (!ctx->codec_stream) HIPCHK(hipStreamCreateWithFlags(&ctx->codec_stream, hipStreamNonBlocking));
+    const int64_t slab = std::min(codec_slab_bytes(), std::max<int64_t>(total, 1));
+    const int64_t ns = (total + slab - 1) / slab;
+    CodecStage stg;
+    HIPCHK(stg.init((size_t)slab, ns > 1 ? 2 : 1));
+    const CodecCells M{d_state.p, links ? d_merge.p : nullptr, d_cell_node.p, d_offsets.p, h.rows(),
+                       h.spacing(), h.bottom_left().x, h.bottom_left().y};
+    auto drain = [&](int64_t j) -> hipError_t {   // slab j from its pinned buffer into buf
+        hipError_t e = hipEventSynchronize(stg.done[j & 1]);
+        if (e != hipSuccess) return e;
+        const int64_t s0 = j * slab, s1 = std::min(total, s0 + slab);
+        std::memcpy(rec + s0, stg.pin[j & 1], (size_t)(s1 - s0));
+        return hipSuccess;
+    };
+    for (int64_t j = 0; j < ns; j++) {
+        const int b = (int)(j & 1);
+        if (j >= 2) HIPCHK(drain(j - 2));
+        const int64_t s0 = j * slab, s1 = std::min(total, s0 + slab);
+        // the cells whose records meet [s0, s1)
+        const int64_t c0 = (std::upper_bound(off.begin(), off.end(), s0) - off.begin()) - 1;
+        const int64_t c1 = std::lower_bound(off.begin(), off.end(), s1) - off.begin();
+        hipLaunchKernelGGL(cc_cells_kernel, dim3((unsigned)((c1 - c0 + CC_THREADS - 1) / CC_THREADS)), dim3(CC_THREADS), 0, s,
+                           M, g->gridconn.p, c0, c1, s0, s1, stg.dev[b].p);
+        hipLaunchKernelGGL(cc_nodes_kernel, dim3((unsigned)(c1 - c0)), dim3(CC_THREADS), 0, s, M, g->pool.p,
+                           g->node_run_start.p, g->bin_nruns.p, g->bin_count.p, g->bin_dist.p, c0, c1, s0, s1,
+                           stg.dev[b].p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(stg.kernel[b], s));
+        HIPCHK(hipStreamWaitEvent(ctx->codec_stream, stg.kernel[b], 0));
+        HIPCHK(hipMemcpyAsync(stg.pin[b], stg.dev[b].p, (size_t)(s1 - s0), hipMemcpyDeviceToHost, ctx->codec_stream));
+        HIPCHK(hipEventRecord(stg.done[b], ctx->codec_stream));
+    }
+    for (int64_t j = std::max<int64_t>(ns - 2, 0); j < ns; j++) HIPCHK(drain(j));
+    HIPCHK(hipStreamSynchronize(s));
+    std::memcpy(rec + total, tail.data(), tail.size());
+    return DMX_OK;
+}
+
+int dmx_chunk_scan(const uint8_t* buf, int64_t size, int32_t* cols, int32_t* rows, int64_t* nnodes, int64_t* nruns,
+                   int64_t* bytes_used) {
+    if (!buf || size <= 0) return fail(DMX_ERR_ARG, "bad arguments");
+    ChunkScan sc;
+    std::string err;
+    if (scan_pointmap_chunk(buf, (size_t)size, false, sc, err)) return fail(DMX_ERR_ARG, err);
+    if (cols) *cols = sc.cols;
+    if (rows) *rows = sc.rows;
+    if (nnodes) *nnodes = sc.nnodes;
+    if (nruns) *nruns = sc.nruns;
+    if (bytes_used) *bytes_used = (int64_t)sc.bytes_used;
+    return DMX_OK;
+}
+
+int dmx_chunk_load_bytes(dmx_ctx* ctx, const uint8_t* buf, int64_t size, const double* region, dmx_pointmap** pm_out,
+                         dmx_graph** g_out) {
+    if (!ctx || !buf || size <= 0 || !region || !pm_out || !g_out) return fail(DMX_ERR_ARG, "bad arguments");
+    ChunkScan sc;
+    {
+        std::string err;
+        if (scan_pointmap_chunk(buf, (size_t)size, true, sc, err)) return fail(DMX_ERR_ARG, err);
+    }
+    if (!sc.processed) return fail(DMX_ERR_STATE, "the point map has no graph (run VISPREP -pm first)");
+    Rect r{region[0], region[1], region[2], region[3]};
+    std::unique_ptr<dmx_pointmap> pm(new dmx_pointmap());
+    pm->host.reset(new PointMapHost(r, sc.spacing, nullptr, 0));
+    pm->host->load_state(sc.cols, sc.rows, sc.spacing, Vec2{sc.blx, sc.bly}, sc.state.data());
+    HIPCHK(hipSetDevice(ctx->device));
+    if (int rc = upload_pointmap(ctx, pm.get())) return rc;
+    const int64_t N = sc.nnodes, N1 = std::max<int64_t>(N, 1);
+    if (N != pm->nnodes) return fail(DMX_ERR_ARG, "node count does not match the filled cells of the map");
+    // the three makeGraph attributes, where the table has the column and a row for every node
+    std::vector<float> attrs((size_t)N1 * 3, 0.0f);
+    if (sc.nrows == N)
+        for (int64_t k = 0; k < N; k++)
+            for (int j = 0; j < 3; j++)
+                if (sc.has_attr[j]) attrs[k * 3 + j] = sc.attrs[k * 3 + j];
+    std::vector<int64_t> start((size_t)N1, 0);
+    int64_t acc = 0, longest = 0;
+    for (int64_t k = 0; k < N; k++) {
+        start[k] = acc;
+        acc += sc.node_nruns[k];
+        longest = std::max<int64_t>(longest, sc.node_len[k]);
+    }
+    std::unique_ptr<dmx_graph> g(new dmx_graph());
+    g->ctx = ctx; g->pm = pm.get(); g->nnodes = N; g->node_begin = 0; g->node_end = N; g->nruns = acc;
+    HIPCHK(g->pool.alloc(std::max<int64_t>(acc, 1)));
+    HIPCHK(g->node_run_start.alloc(N1));
+    HIPCHK(g->node_nruns.alloc(N1));
+    HIPCHK(g->bin_nruns.alloc(N1 * 32));
+    HIPCHK(g->bin_count.alloc(N1 * 32));
+    HIPCHK(g->bin_dist.alloc(N1 * 32));
+    HIPCHK(g->attrs.alloc(N1 * 3));
+    HIPCHK(g->gridconn.alloc(N1));
+    hipStream_t s = ctx->stream;
+    DevBuf<int64_t> d_off;
+    HIPCHK(d_off.alloc(N1));
+    if (N) {
+        HIPCHK(hipMemcpyAsync(g->node_run_start.p, start.data(), N * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g->node_nruns.p, sc.node_nruns.data(), N * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g->attrs.p, attrs.data(), N * 12, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g->gridconn.p, sc.gridconn.data(), N, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_off.p, sc.node_off.data(), N * 8, hipMemcpyHostToDevice, s));
+        // the node records, slab by slab: whole nodes whose bins lie within one slab's bytes of each other (a node
+        // longer than the slab goes alone); the bytes between them (occlusion bins, cells without a node) ride along
+        const int64_t slab = std::max(std::min(codec_slab_bytes(), sc.node_off[N - 1] + sc.node_len[N - 1] - sc.node_off[0]),
+                                      longest);
+        CodecStage stg;
+        HIPCHK(stg.init((size_t)slab, 2));
+        int64_t k0 = 0;
+        for (int64_t j = 0; k0 < N; j++) {
+            const int b = (int)(j & 1);
+            const int64_t f0 = sc.node_off[k0];
+            int64_t k1 = k0 + 1;
+            while (k1 < N && sc.node_off[k1] + sc.node_len[k1] - f0 <= slab) k1++;
+            const int64_t f1 = sc.node_off[k1 - 1] + sc.node_len[k1 - 1];
+            if (j >= 2) HIPCHK(hipEventSynchronize(stg.done[b]));   // the buffers' previous slab is decoded
+            std::memcpy(stg.pin[b], buf + f0, (size_t)(f1 - f0));
+            HIPCHK(hipMemcpyAsync(stg.dev[b].p, stg.pin[b], (size_t)(f1 - f0), hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(cc_decode_kernel, dim3((unsigned)(k1 - k0)), dim3(CC_THREADS), 0, s, stg.dev[b].p, f0, d_off.p,
+                               g->node_run_start.p, k0, k1, g->pool.p, g->bin_nruns.p, g->bin_count.p, g->bin_dist.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(stg.done[b], s));
+            k0 = k1;
+        }
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    {
+        std::vector<int32_t> per_cell, uniq;
+        int rc = normalize_merges(pm->host->cells(), sc.merge_pairs.data(), (int64_t)sc.merge_pairs.size() / 2, per_cell,
+                                  uniq, true);
+        if (rc) return rc;
+        pm->host->set_merge(std::move(per_cell));
+    }
+    inherit_merges(g.get());
+    *pm_out = pm.release();
+    *g_out = g.release();
     return DMX_OK;
 }
 

@@ -520,18 +520,21 @@ struct VisPrep : Mode {
                 int64_t n = 0, b, e, nr = 0;
                 check(dmx_graph_info(g, &n, &b, &e, &nr));
                 std::vector<float> attrs((size_t)n * 3);
-                std::vector<int32_t> bins((size_t)n * 128);
-                std::vector<int16_t> runs((size_t)std::max<int64_t>(nr, 1) * 4);
-                std::vector<uint8_t> gc((size_t)n);
-                check(dmx_graph_copy(g, attrs.data(), bins.data(), runs.data(), gc.data()));
-                dmx_graph_free(g);
+                check(dmx_graph_copy(g, attrs.data(), nullptr, nullptr, nullptr));
                 // sparkGraph2 columns (pointdata.cpp:1268-1270), displayed = Connectivity
-                const std::vector<std::string> names = {"Connectivity", "Point First Moment", "Point Second Moment"};
-                std::vector<std::vector<float>> cols(3, std::vector<float>((size_t)n));
+                const char* names[3] = {"Connectivity", "Point First Moment", "Point Second Moment"};
+                std::vector<float> cols((size_t)n * 3);
                 for (int j = 0; j < 3; j++)
-                    for (int64_t k = 0; k < n; k++) cols[j][k] = attrs[k * 3 + j];
-                out = write_chunk(pm, n, bins.data(), runs.data(), nr, gc.data(), names, cols, {1, 0, 0}, 0, boundary,
-                                  map_name);
+                    for (int64_t k = 0; k < n; k++) cols[(size_t)j * n + k] = attrs[k * 3 + j];
+                const uint8_t locked[3] = {1, 0, 0};
+                // the node records are encoded on the GPU, straight from the graph (dmx_graph_chunk_write)
+                int64_t size = 0;
+                check(dmx_graph_chunk_write(g, map_name.c_str(), 3, names, cols.data(), locked, nullptr, 0, boundary ? 1 : 0,
+                                            nullptr, 0, &size));
+                out.resize((size_t)size);
+                check(dmx_graph_chunk_write(g, map_name.c_str(), 3, names, cols.data(), locked, nullptr, 0, boundary ? 1 : 0,
+                                            out.data(), size, &size));
+                dmx_graph_free(g);
             } else {
                 out = write_chunk(pm, 0, nullptr, nullptr, 0, nullptr, {}, {}, {}, -2, false, map_name);
             }

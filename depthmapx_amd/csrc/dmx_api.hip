@@ -40,6 +40,7 @@
 #include "kernels/thruvision.hip"
 #include "kernels/isovist.hip"
 #include "kernels/isovist_points.hip"
+#include "kernels/chunk_codec.hip"
 
 using namespace dmx;
 
@@ -189,6 +190,7 @@ struct dmx_ctx {
     int device = 0;
     bool tile_disabled = false;
     hipStream_t stream = nullptr;
+    hipStream_t codec_stream = nullptr;   // the chunk encoder's device-to-host copies (beside the next slab's kernels)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int num_cu = 0;
     double last_mk_s = 0, last_vga_s = 0, last_sd_s = 0;
@@ -698,6 +700,7 @@ int dmx_ctx_free(dmx_ctx* c) {
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->ev_poll) (void)hipEventDestroy(c->ev_poll);
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
+    if (c->codec_stream) (void)hipStreamDestroy(c->codec_stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return DMX_OK;

@@ -87,14 +87,13 @@ Stats replay_stats(const float* v, const uint8_t* set, int64_t n) {
 }
 } // namespace
 
-int write_pointmap_chunk(const PointMapHost& h, int64_t nnodes, const int32_t* bins, const int16_t* runs, int64_t nruns,
-                         const uint8_t* gridconn, const std::vector<ChunkColumn>& cols, int displayed, bool boundary,
-                         std::vector<uint8_t>& out, std::string& err) {
+int write_pointmap_head(const PointMapHost& h, int64_t nnodes, bool graph, const std::vector<ChunkColumn>& cols,
+                        int displayed, const std::string& name, bool reread, std::vector<uint8_t>& out, std::string& err) {
     out.clear();
     Writer w{out};
     const int C_cols = h.cols(), C_rows = h.rows();
     // ---- PointMap header (pointdata.cpp:1160-1176)
-    w.str("VGA Map");
+    w.str(name);
     w.put<double>(h.spacing());
     w.put<int32_t>(C_rows);
     w.put<int32_t>(C_cols);
@@ -103,7 +102,6 @@ int write_pointmap_chunk(const PointMapHost& h, int64_t nnodes, const int32_t* b
     w.put<double>(h.bottom_left().y);
     // no graph (VISPREP without -pm): no Node records, an empty attribute table (rows are added by
     // sparkGraph2, pointdata.cpp:1294), m_processed false, displayed attribute -2
-    const bool graph = bins != nullptr;
     if (!graph) nnodes = 0;
     std::vector<int> order(cols.size());
     std::iota(order.begin(), order.end(), 0);
@@ -113,6 +111,13 @@ int write_pointmap_chunk(const PointMapHost& h, int64_t nnodes, const int32_t* b
         if (order[i] == displayed) sorted_disp = (int)i;
     if (displayed < 0) sorted_disp = displayed;
     if (!graph) sorted_disp = -2;
+    if (reread && sorted_disp >= 0) {
+        // PointMap::read keeps the sorted index it read as a physical one and ::write sorts it again
+        // (read_pointmap_chunk, write_parsed_chunk)
+        const int phys = sorted_disp;
+        for (size_t i = 0; i < order.size(); i++)
+            if (order[i] == phys) sorted_disp = (int)i;
+    }
     w.put<int32_t>(sorted_disp);
     // ---- AttributeTable::write: layer manager with the single "Everything" layer
     w.put<int64_t>(0xC0000000LL);   // availableLayers = 0xffffffff << (32 + 0xfffffffe) (unsigned wrap: << 30)
@@ -155,6 +160,24 @@ int write_pointmap_chunk(const PointMapHost& h, int64_t nnodes, const int32_t* b
     w.put<float>(0.0f);   // table DisplayParams
     w.put<float>(1.0f);
     w.put<int32_t>(0);
+    return 0;
+}
+
+void write_pointmap_tail(bool graph, bool boundary, std::vector<uint8_t>& out) {
+    Writer w{out};
+    w.put<uint8_t>(graph ? 1 : 0);     // m_processed
+    w.put<uint8_t>(graph && boundary ? 1 : 0);  // m_boundarygraph
+}
+
+int write_pointmap_chunk(const PointMapHost& h, int64_t nnodes, const int32_t* bins, const int16_t* runs, int64_t nruns,
+                         const uint8_t* gridconn, const std::vector<ChunkColumn>& cols, int displayed, bool boundary,
+                         std::vector<uint8_t>& out, std::string& err) {
+    const int C_cols = h.cols(), C_rows = h.rows();
+    const bool graph = bins != nullptr;
+    if (!graph) nnodes = 0;
+    if (write_pointmap_head(h, nnodes, graph, cols, displayed, "VGA Map", false, out, err)) return -1;
+    Writer w{out};
+    const auto& st = h.state();
     // ---- points, x-major (ColumnMatrix storage order)
     int64_t k = 0, ro = 0;
     for (int x = 0; x < C_cols; x++)
@@ -218,8 +241,7 @@ int write_pointmap_chunk(const PointMapHost& h, int64_t nnodes, const int32_t* b
             w.put<double>(loc.y);
         }
     if (graph && ro != nruns) { err = "run count does not match the bins"; return -1; }
-    w.put<uint8_t>(graph ? 1 : 0);     // m_processed
-    w.put<uint8_t>(graph && boundary ? 1 : 0);  // m_boundarygraph
+    write_pointmap_tail(graph, boundary, out);
     return 0;
 }
 
@@ -579,6 +601,133 @@ int read_pointmap_chunk(const uint8_t* buf, size_t size, ParsedChunk& pc, std::s
     pc.boundary = r.get<uint8_t>() != 0;
     if (!r.ok) { err = "truncated PointMap chunk"; return -1; }
     pc.bytes_used = r.o;
+    return 0;
+}
+
+// The same walk as read_pointmap_chunk with nothing decoded: the attribute rows are read for the three makeGraph
+// columns only, a bin is hopped over from its header (dir, node count, and the run count of an H / V bin), the
+// occlusion bins from their counts.  Every hop is checked against `size` before it is taken, so the extents this
+// leaves in `sc` (node_off / node_len) lie inside the buffer and hold exactly the bytes the reader would decode.
+int scan_pointmap_chunk(const uint8_t* buf, size_t size, bool keep, ChunkScan& sc, std::string& err) {
+    Reader r{buf, size};
+    auto skip = [&](size_t n) {
+        if (!r.ok || n > size - std::min(r.o, size)) { r.ok = false; return; }
+        r.o += n;
+    };
+    sc = ChunkScan();
+    (void)r.str();
+    sc.spacing = r.get<double>();
+    sc.rows = r.get<int32_t>();
+    sc.cols = r.get<int32_t>();
+    (void)r.get<int32_t>();
+    sc.blx = r.get<double>();
+    sc.bly = r.get<double>();
+    (void)r.get<int32_t>();
+    (void)r.get<int64_t>();
+    (void)r.get<int64_t>();
+    const int32_t nlayers = r.get<int32_t>();
+    for (int i = 0; i < nlayers && r.ok; i++) {
+        (void)r.get<int64_t>();
+        (void)r.str();
+    }
+    if (!r.ok || nlayers < 0) { err = "not a PointMap chunk"; return -1; }
+    const int32_t ncols = r.get<int32_t>();
+    if (!r.ok || ncols < 0 || ncols > 4096 || sc.rows <= 0 || sc.cols <= 0) { err = "not a PointMap chunk"; return -1; }
+    static const char* const mk[3] = {"Connectivity", "Point First Moment", "Point Second Moment"};
+    std::vector<std::string> names(ncols);   // by physical column
+    std::vector<std::string> sorted(ncols);
+    std::vector<int> phys(ncols);
+    for (int i = 0; i < ncols && r.ok; i++) {
+        sorted[i] = r.str();
+        (void)r.get<float>();
+        (void)r.get<float>();
+        (void)r.get<double>();
+        phys[i] = r.get<int32_t>();
+        (void)r.get<uint8_t>();
+        (void)r.get<uint8_t>();
+        r.o += 12;
+        (void)r.str();
+    }
+    for (int i = 0; i < ncols; i++) {
+        if (phys[i] < 0 || phys[i] >= ncols) { err = "bad physical column"; return -1; }
+        names[phys[i]] = sorted[i];
+    }
+    int mkcol[3] = {-1, -1, -1};   // the last physical column of each name, as dmx_chunk_load takes it
+    for (int j = 0; j < 3; j++)
+        for (int i = 0; i < ncols; i++)
+            if (names[i] == mk[j]) mkcol[j] = i;
+    const int32_t nrows = r.get<int32_t>();
+    if (!r.ok || nrows < 0 || (size_t)nrows * 16 > size - r.o) { err = "truncated attribute table"; return -1; }
+    sc.nrows = nrows;
+    if (keep) sc.attrs.assign((size_t)nrows * 3, -1.0f);
+    for (int j = 0; j < 3; j++) sc.has_attr[j] = mkcol[j] >= 0;
+    for (int32_t i = 0; i < nrows && r.ok; i++) {
+        (void)r.get<int32_t>();
+        (void)r.get<int64_t>();
+        const uint32_t n = r.get<uint32_t>();
+        if (!r.ok || (size_t)n * 4 > size - std::min(r.o, size)) { r.ok = false; break; }
+        if (keep)
+            for (int j = 0; j < 3; j++)
+                if (mkcol[j] >= 0 && (uint32_t)mkcol[j] < n)
+                    std::memcpy(&sc.attrs[(size_t)i * 3 + j], buf + r.o + (size_t)mkcol[j] * 4, 4);
+        r.o += (size_t)n * 4;
+    }
+    r.o += 12;
+    const int64_t C = (int64_t)sc.cols * sc.rows;
+    if (r.o > size || (uint64_t)C * 30 > (uint64_t)(size - r.o)) { err = "truncated point records"; return -1; }
+    if (keep) sc.state.resize((size_t)C);
+    for (int x = 0; x < sc.cols && r.ok; x++)
+        for (int y = 0; y < sc.rows && r.ok; y++) {
+            const int32_t st = r.get<int32_t>();
+            (void)r.get<int32_t>();
+            (void)r.get<int32_t>();
+            const int8_t gc = r.get<int8_t>();
+            const int32_t merge = r.get<int32_t>();
+            const bool node = r.get<uint8_t>() != 0;
+            if (!r.ok) break;
+            if (keep) {
+                sc.state[(size_t)x * sc.rows + y] = st;
+                if (merge != -1) {
+                    const int mx = (int16_t)(merge & 0xFFFF), my = (int16_t)((uint32_t)merge >> 16);
+                    sc.merge_pairs.push_back((int32_t)((int64_t)x * sc.rows + y));
+                    sc.merge_pairs.push_back((int32_t)((int64_t)mx * sc.rows + my));
+                }
+            }
+            if (node) {
+                const size_t n0 = r.o;
+                int64_t nr = 0;
+                for (int b = 0; b < 32 && r.ok; b++) {
+                    const uint8_t dir = r.get<uint8_t>();
+                    const uint16_t count = r.get<uint16_t>();
+                    skip(8);   // distance, m_occ_distance
+                    if (count) {
+                        if (dir & DIR_DIAG) {
+                            skip(6);
+                            nr += 1;
+                        } else {
+                            const uint16_t n = r.get<uint16_t>();
+                            skip(6 + (n ? (size_t)(n - 1) * 4 : 0));
+                            nr += n;
+                        }
+                    }
+                }
+                if (!r.ok) break;
+                if (keep) {
+                    sc.gridconn.push_back((uint8_t)gc);
+                    sc.node_off.push_back((int64_t)n0);
+                    sc.node_len.push_back((int32_t)(r.o - n0));   // at most 32 * (13 + 6 + 4 * 65534) bytes
+                    sc.node_nruns.push_back((int32_t)nr);
+                }
+                sc.nnodes++;
+                sc.nruns += nr;
+                for (int b = 0; b < 32 && r.ok; b++) skip((size_t)r.get<uint32_t>() * 4);
+            }
+            skip(16);   // m_location
+        }
+    sc.processed = r.get<uint8_t>() != 0;
+    sc.boundary = r.get<uint8_t>() != 0;
+    if (!r.ok) { err = "truncated PointMap chunk"; return -1; }
+    sc.bytes_used = r.o;
     return 0;
 }
 

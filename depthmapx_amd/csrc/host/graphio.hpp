@@ -54,7 +54,39 @@ struct ParsedChunk {
 int write_pointmap_chunk(const PointMapHost& h, int64_t nnodes, const int32_t* bins, const int16_t* runs, int64_t nruns,
                          const uint8_t* gridconn, const std::vector<ChunkColumn>& cols, int displayed, bool boundary,
                          std::vector<uint8_t>& out, std::string& err);
+// The two parts of PointMap::write around the point records, for writers that produce the records themselves
+// (write_pointmap_chunk, dmx_graph_chunk_write).  Head: the map header under `name`, the layer block, the columns
+// with replayed statistics, the attribute rows (checked against nnodes) and the table's display parameters.
+// `reread`: the bytes PointMap::read followed by ::write would give for it (write_parsed_chunk of the parsed
+// chunk): the displayed index read as a physical column and sorted again; the caller masks the point states with
+// kChunkStateMask.  Tail: m_processed, m_boundarygraph.
+int write_pointmap_head(const PointMapHost& h, int64_t nnodes, bool graph, const std::vector<ChunkColumn>& cols,
+                        int displayed, const std::string& name, bool reread, std::vector<uint8_t>& out, std::string& err);
+void write_pointmap_tail(bool graph, bool boundary, std::vector<uint8_t>& out);
+// the Point::m_state bits PointMap::read keeps (pointdata.cpp:1128)
+constexpr int32_t kChunkStateMask = CELL_EMPTY | CELL_FILLED | CELL_MERGED | CELL_BLOCKED | CELL_CONTEXTFILLED | CELL_EDGE;
 int read_pointmap_chunk(const uint8_t* buf, size_t size, ParsedChunk& pc, std::string& err);
+
+// What a walk over a chunk's records finds without decoding them (scan_pointmap_chunk).
+struct ChunkScan {
+    double spacing = 0, blx = 0, bly = 0;
+    int32_t rows = 0, cols = 0;
+    int64_t nnodes = 0, nruns = 0, nrows = 0;
+    bool processed = false, boundary = false;
+    size_t bytes_used = 0;
+    // kept on request (keep): what a device graph needs beside the node records' bytes
+    std::vector<int32_t> state;         // [cols*rows] x-major, as stored
+    std::vector<uint8_t> gridconn;      // [N]
+    std::vector<int32_t> merge_pairs;   // (cell, partner) of every point with a merge link
+    std::vector<int64_t> node_off;      // [N] offset of the node's first bin header in the chunk
+    std::vector<int32_t> node_len;      // [N] bytes of its 32 bins (headers and run payloads)
+    std::vector<int32_t> node_nruns;    // [N] runs its bins decode to
+    std::vector<float> attrs;           // [nrows][3] the makeGraph columns' values (-1 where a row has none)
+    bool has_attr[3] = {false, false, false};
+};
+// Header, attribute table, then from bin header to bin header (32 a node, and its 32 occlusion counts), every
+// record's end checked against `size`; errors are read_pointmap_chunk's.
+int scan_pointmap_chunk(const uint8_t* buf, size_t size, bool keep, ChunkScan& sc, std::string& err);
 // PointMap::write of a chunk read earlier and edited through the helpers below: header, attribute
 // table (columns alphabetically; read columns keep their stats, set columns replay them), the point
 // records as read (state bits masked as PointMap::read masks them), processed / boundary flags.

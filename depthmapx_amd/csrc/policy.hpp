@@ -74,6 +74,12 @@ constexpr int kIsoPointsWavesPerCu = 16;
 // (profiles/isovist_points.jsonl).  Hook: DMX_ISO_ORDER (caller | morton).
 constexpr int kIsoPointsMorton = 1;
 
+// ---- .graph chunk codec (chunk_codec.hip, api/chunk.hip)
+// bytes of the record stream a slab holds: two slabs in device memory and two in pinned host memory, whatever the
+// size of the chunk (18.5 GB at 1000^2).  A slab is a byte range, so a record larger than it spans several.  64 MiB
+// keeps the pinned allocation short next to the copy it serves.  Hook: DMX_CODEC_SLAB (bytes; tests shrink it).
+constexpr int64_t kCodecSlabBytes = 64ll << 20;
+
 // ---- memory: optional summaries are built only within a share of the free device memory, so a graph
 // that fills the GPU still runs (on the slower exact path that needs no summary)
 // tile rows (tvis / ftvis) and partial-tile masks on narrow grids: a quarter of the free memory

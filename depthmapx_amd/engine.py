@@ -389,6 +389,13 @@ class Graph:
             out["runs"] = rr[:nr.value]
         return out
 
+    def write_chunk(self, columns, displayed=0, boundary=False, name=None):
+        """The map's .graph PointMap chunk with this graph's nodes, as bytes: what graphio.write_chunk gives for
+        copy()'s arrays, with the node records encoded on the GPU and no host copy of the runs
+        (dmx_graph_chunk_write).  columns as in graphio.write_chunk; name: the map's name if not "VGA Map"."""
+        from . import graphio
+        return graphio.write_chunk_device(self, columns, displayed=displayed, boundary=boundary, name=name)
+
     def set_merges(self, cell_pairs):
         """Merge links followed by VGA global, visual / metric / angular step depth and VGA metric /
         angular (the getMergePixel blocks of salalib/vgamodules); pairs of x-major cells."""

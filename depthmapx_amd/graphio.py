@@ -12,13 +12,9 @@ import numpy as np
 from . import _native as N
 
 
-def write_chunk(pm, bins, runs, gridconn, columns, displayed=0, boundary=False):
-    """columns: list of (name, values[N] float32, locked[, setmask[N]]) in insertion order
-    (MAKEGRAPH_COLUMNS after VISPREP, then the VGA columns); displayed indexes that list."""
-    bins = np.ascontiguousarray(bins, dtype=np.int32)
-    runs = np.ascontiguousarray(runs, dtype=np.int16).reshape(-1, 4)
-    gridconn = np.ascontiguousarray(gridconn, dtype=np.uint8)
-    n = bins.shape[0]
+def _column_args(columns, n):
+    """The column arguments of dmx_chunk_write / dmx_graph_chunk_write: (ncols, names, values, locked, setmask);
+    the arrays are kept alive by the tuple."""
     names = (ctypes.c_char_p * max(len(columns), 1))(*[c[0].encode() for c in columns])
     vals = np.ascontiguousarray(np.stack([np.asarray(c[1], dtype=np.float32) for c in columns]) if columns
                                 else np.zeros((0, n), np.float32))
@@ -27,8 +23,34 @@ def write_chunk(pm, bins, runs, gridconn, columns, displayed=0, boundary=False):
     if any(len(c) > 3 and c[3] is not None for c in columns):
         masks = np.ascontiguousarray(np.stack([np.asarray(c[3], dtype=np.uint8) if (len(c) > 3 and c[3] is not None)
                                                else np.ones(n, np.uint8) for c in columns]))
+    return len(columns), names, vals, locked, masks
+
+
+def write_chunk_device(g, columns, displayed=0, boundary=False, name=None):
+    """PointMap::write of the graph's map with its nodes, the node records encoded on the GPU
+    (dmx_graph_chunk_write): the bytes of write_chunk(pm, *g.copy()...), without the copy.  name: the map's
+    name where it is not "VGA Map"."""
+    n = g.info()["nnodes"]
+    nc, names, vals, locked, masks = _column_args(columns, n)
     size = ctypes.c_int64()
-    args = [pm.h, n, N.ptr(bins), N.ptr(runs), len(runs), N.ptr(gridconn), len(columns), names, N.ptr(vals),
+    args = [g.h, None if name is None else name.encode(), nc, names, N.ptr(vals), N.ptr(locked), N.ptr(masks),
+            int(displayed), int(bool(boundary))]
+    N.check(N.lib().dmx_graph_chunk_write(*args, None, 0, ctypes.byref(size)))
+    buf = np.empty(size.value, dtype=np.uint8)
+    N.check(N.lib().dmx_graph_chunk_write(*args, N.ptr(buf), size.value, ctypes.byref(size)))
+    return buf.tobytes()
+
+
+def write_chunk(pm, bins, runs, gridconn, columns, displayed=0, boundary=False):
+    """columns: list of (name, values[N] float32, locked[, setmask[N]]) in insertion order
+    (MAKEGRAPH_COLUMNS after VISPREP, then the VGA columns); displayed indexes that list."""
+    bins = np.ascontiguousarray(bins, dtype=np.int32)
+    runs = np.ascontiguousarray(runs, dtype=np.int16).reshape(-1, 4)
+    gridconn = np.ascontiguousarray(gridconn, dtype=np.uint8)
+    n = bins.shape[0]
+    nc, names, vals, locked, masks = _column_args(columns, n)
+    size = ctypes.c_int64()
+    args = [pm.h, n, N.ptr(bins), N.ptr(runs), len(runs), N.ptr(gridconn), nc, names, N.ptr(vals),
             N.ptr(locked), N.ptr(masks), int(displayed), int(bool(boundary))]
     N.check(N.lib().dmx_chunk_write(*args, None, 0, ctypes.byref(size)))
     buf = np.zeros(size.value, dtype=np.uint8)
@@ -93,6 +115,47 @@ def load_chunk(ctx, blob, region, lines=None):
     pm.h = hp
     info = read_chunk(blob)
     pm.spacing = info["spacing"]
+    g = Graph(hg, ctx, pm)
+    if lines is not None:
+        g.set_drawing(lines)
+    return pm, g
+
+
+def scan_chunk(blob):
+    """A walk over the chunk's records without decoding them (dmx_chunk_scan; host only): cols, rows, nnodes, nruns
+    and bytes_used as read_chunk gives them, and the header's spacing and bottom_left.  DmxError(DMX_ERR_ARG) on a
+    damaged chunk."""
+    buf = np.frombuffer(blob, dtype=np.uint8)
+    cols, rows = ctypes.c_int32(), ctypes.c_int32()
+    nn, nr, used = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    N.check(N.lib().dmx_chunk_scan(N.ptr(buf), len(buf), ctypes.byref(cols), ctypes.byref(rows), ctypes.byref(nn),
+                                   ctypes.byref(nr), ctypes.byref(used)))
+    spacing, bl = _header_geometry(blob)
+    return dict(cols=cols.value, rows=rows.value, nnodes=nn.value, nruns=nr.value, bytes_used=used.value,
+                spacing=spacing, bottom_left=bl)
+
+
+def _header_geometry(blob):
+    """(spacing, bottom left) from the header of a chunk a scan has walked: name, spacing, rows, cols, filled,
+    bottom left."""
+    import struct
+    o = 4 + struct.unpack_from("<I", blob, 0)[0]
+    return struct.unpack_from("<d", blob, o)[0], struct.unpack_from("<dd", blob, o + 20)
+
+
+def load_chunk_device(ctx, blob, region, lines=None):
+    """load_chunk with the node records decoded on the GPU (dmx_chunk_load_bytes): the chunk is scanned, not
+    parsed, and its bytes go to the device as they are."""
+    from .engine import Graph, PointMap
+    buf = np.frombuffer(blob, dtype=np.uint8)
+    reg = np.ascontiguousarray(region, dtype=np.float64)
+    hp, hg = ctypes.c_void_p(), ctypes.c_void_p()
+    N.check(N.lib().dmx_chunk_load_bytes(ctx.h, N.ptr(buf), len(buf), N.ptr(reg), ctypes.byref(hp), ctypes.byref(hg)))
+    pm = PointMap.__new__(PointMap)
+    pm._region = reg
+    pm._lines = np.zeros((0, 4))
+    pm.h = hp
+    pm.spacing = _header_geometry(blob)[0]   # (dmx_chunk_load_bytes has scanned the chunk)
     g = Graph(hg, ctx, pm)
     if lines is not None:
         g.set_drawing(lines)

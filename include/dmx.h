@@ -450,6 +450,29 @@ int dmx_chunk_unmake(dmx_chunk* c, int remove_links);
 /* PointMap::write of the (edited) chunk; buf NULL or cap too small: only *size. */
 int dmx_chunk_serialize(const dmx_chunk* c, uint8_t* buf, int64_t cap, int64_t* size);
 
+/* ---- .graph PointMap chunk, node records on the GPU ------------------------------------------ */
+/* PointMap::write of g's point map with g's nodes; bytes equal dmx_chunk_write(pm, dmx_graph_copy(g)...),
+ * followed, when map_name is not NULL / "VGA Map", by what dmx_chunk_set_name + dmx_chunk_serialize give.
+ * The header, the attribute table and the two flag bytes are written on the host; the Point / Node records
+ * (more than 99 % of the bytes) are encoded on g's device from the graph as it lies there and copied out in
+ * slabs, so neither the runs nor the chunk are held a second time.  columns as in dmx_chunk_write.
+ * buf NULL or cap too small: only *size is set (from the size pass; nothing is encoded).  DMX_ERR_ARG for a
+ * bin with a node count and no runs, DMX_ERR_STATE for a shard (node_begin != 0 or node_end != nnodes). */
+int dmx_graph_chunk_write(dmx_graph* g, const char* map_name, int ncols, const char* const* names,
+                          const float* values, const uint8_t* locked, const uint8_t* setmask, int displayed,
+                          int boundary, uint8_t* buf, int64_t cap, int64_t* size);
+/* Host only: walk a chunk's records without decoding them (header, attribute table, then from bin header to
+ * bin header); every record's end is checked against size, DMX_ERR_ARG with dmx_chunk_parse's messages on
+ * damage.  Any out pointer may be NULL. */
+int dmx_chunk_scan(const uint8_t* buf, int64_t size, int32_t* cols, int32_t* rows, int64_t* nnodes,
+                   int64_t* nruns, int64_t* bytes_used);
+/* dmx_chunk_parse + dmx_chunk_load in one call, node records decoded on the GPU: the scan above validates the
+ * chunk and keeps the cells' state, grid connections, merge links and each node's extent; the bytes are
+ * uploaded in slabs and a kernel writes the graph's runs and bin records in place.  Occlusion data in the
+ * chunk is skipped.  Results and errors are dmx_chunk_load's. */
+int dmx_chunk_load_bytes(dmx_ctx* ctx, const uint8_t* buf, int64_t size, const double* region,
+                         dmx_pointmap** pm, dmx_graph** g);
+
 /* ---- .graph file (host) ---------------------------------------------------------------------- */
 /* The MetaGraph container, METAGRAPH_VERSION 440: MetaGraph::readFromFile / readFromStream
  * (salalib/mgraph.cpp:2475-2654) and MetaGraph::write(file, 440, false) (mgraph.cpp:2656-2757, as
