@@ -172,12 +172,14 @@ static int stepdepth_impl(dmx_ctx* ctx, dmx_graph* g, const int32_t* sel_cells, 
     HIPCHK(hipMemcpyAsync(d_flags.p, flags.data(), C, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_sel.p, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, s));
     int64_t cap = 8 * (nexp + (int64_t)sel.size()) + SD_WIN + 1024 + (ANG ? 8 * N : 0);
+    if (const char* e = getenv("DMX_SD_CAP")) cap = std::max<int64_t>(64, atoll(e));   // test hook: retries
     // metric: the batched search over the whole GPU (stepdepth.hip, "batched metric step depth");
     // DMX_SD_KERNEL=serial forces the one-workgroup kernel, which is also the fallback
     // (merge links: the serial kernel, which extracts a partner at its link's pop)
     bool batched = !ANG && g->merges.empty();
     if (const char* e = getenv("DMX_SD_KERNEL")) batched = batched && strcmp(e, "serial") != 0;
     ctx->last_sd_mode = 0;
+    ctx->last_sd_attempts = 0;
     if (batched) {
         int rc = stepdepth_batched(ctx, g, flags, sel, d_flags.p, d_sel.p, d_key.p, d_mdist.p, d_cum.p, d_last.p);
         if (rc < 0) return rc;
@@ -198,6 +200,7 @@ static int stepdepth_impl(dmx_ctx* ctx, dmx_graph* g, const int32_t* sel_cells, 
         ctx->last_sd_mode = 2;
     }
     for (int attempt = 0; attempt < 4; attempt++) {
+        ctx->last_sd_attempts = attempt + 1;
         HIPCHK(d_over.alloc(cap));
         HIPCHK(hipMemsetAsync(d_key.p, 0xFF, C * 8, s));
         std::vector<float> m1((size_t)C, -1.0f);
@@ -474,6 +477,12 @@ int dmx_ctx_last_stepdepth(dmx_ctx* ctx, double* seconds, int64_t* expanders_pop
     if (seconds) *seconds = ctx->last_sd_s;
     if (expanders_popped) *expanders_popped = ctx->last_sd_stats[0];
     if (cells_relaxed) *cells_relaxed = ctx->last_sd_stats[1];
+    return DMX_OK;
+}
+
+int dmx_ctx_last_stepdepth_attempts(dmx_ctx* ctx, int64_t* attempts) {
+    if (!ctx || !attempts) return fail(DMX_ERR_ARG, "bad arguments");
+    *attempts = ctx->last_sd_attempts;
     return DMX_OK;
 }
 

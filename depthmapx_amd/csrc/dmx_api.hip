@@ -194,7 +194,8 @@ struct dmx_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int num_cu = 0;
     double last_mk_s = 0, last_vga_s = 0, last_sd_s = 0;
-    long long last_sd_stats[3] = {0, 0, 0};   // expanders popped, cells relaxed, batches (serial: refills)
+    long long last_sd_stats[3] = {0, 0, 0};   // expanders popped, cells relaxed, batches (serial, VGA metric / angular: refills)
+    int last_sd_attempts = 0;                 // serial step depth: kernel launches (1 + overflow-list retries); batched: 0
     long long last_sd_extra[2] = {0, 0};      // batched: improved cells, ambiguous cells
     int last_sd_mode = 0;                     // 0 serial, 1 batched, 2 batched overflow -> serial
     long long phase_cycles[5] = {0, 0, 0, 0, 0};   // tile BFS: level 1, A, B, C, bookkeeping (sum over workgroups)

@@ -216,7 +216,6 @@ __device__ void sd_run(SdShared& S, const StepDepthParams& P, const int32_t* sel
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     unsigned long long& s_keep = S.keep;
     int& s_idx = S.idx;
-    int& s_cnt = S.cnt;
     if (tid == 0) {
         S.nwin = 0; S.nchunk = 0; S.gmin = SD_INF; S.nover = 0; S.cut_w = 4.0f; S.ovf = 0;
     }
@@ -260,21 +259,52 @@ __device__ void sd_run(SdShared& S, const StepDepthParams& P, const int32_t* sel
             if (tid == 0) S.nwin = 0;
             const long long no = min(S.nover, P.over_cap);
             const unsigned long long g0 = S.gmin;
+            // keys of the list below c0 (low word) and below c1 (high word); the same value in every thread
+            auto count_below = [&](unsigned long long c0, unsigned long long c1) -> unsigned long long {
+                unsigned long long n = 0;
+                for (long long i = tid; i < no; i += SD_THREADS) {
+                    const unsigned long long k = P.over[i];
+                    n += (k < c0 ? 1ull : 0ull) + (k < c1 ? 1ull << 32 : 0ull);
+                }
+                for (int off = 32; off >= 1; off >>= 1) n += (unsigned long long)__shfl_xor(n, off);
+                if (tid == 0) s_keep = 0;
+                __syncthreads();
+                if (lane == 0) atomicAdd(&s_keep, n);
+                __syncthreads();
+                n = s_keep;
+                __syncthreads();
+                return n;
+            };
+            // Any cut above g0 is valid: the window only has to hold every valid key below it.  A cut by
+            // distance cannot go below `tie`, the first key past the smallest distance d0.
+            const unsigned long long d0hi = g0 | 0xffffffffull;
+            const unsigned long long tie = d0hi == SD_INF ? SD_INF : d0hi + 1ull;
+            const float d0 = __uint_as_float((unsigned)(g0 >> 32));
             unsigned long long cut;
             for (;;) {
-                const float d0 = __uint_as_float((unsigned)(g0 >> 32));
-                cut = max(sd_key(d0 + S.cut_w, 0), g0 + 1ull);
-                int cnt = 0;
-                for (long long i = tid; i < no; i += SD_THREADS) cnt += (P.over[i] < cut) ? 1 : 0;
-                for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off);
-                if (tid == 0) s_cnt = 0;
-                __syncthreads();
-                if (lane == 0) atomicAdd(&s_cnt, cnt);
-                __syncthreads();
-                const int total = s_cnt;
-                __syncthreads();
-                if (total <= SD_WIN || cut == g0 + 1ull) {
-                    if (tid == 0 && total < SD_WIN / 8) S.cut_w *= 2.0f;
+                cut = max(sd_key(d0 + S.cut_w, 0), tie);
+                const unsigned long long n = count_below(cut, tie);
+                const unsigned total = (unsigned)n, ties = (unsigned)(n >> 32);
+                if (ties > (unsigned)SD_WIN) {
+                    // More keys at d0 itself than the window holds (angular: every cell the source sees is
+                    // queued at angle 0): no width narrows that, so the keys at d0 are split by their
+                    // PixelRef bits -- the largest cut that admits at most a window, or the first found that
+                    // admits an eighth of one.  cut_w keeps its value for the distances after d0.
+                    const unsigned long long base = g0 & ~0xffffffffull;
+                    unsigned pc = 0;
+                    for (int bit = 47 - __clz(max(P.cols, 1)); bit >= 0; bit--) {   // PixelRef < cols << 16
+                        const unsigned m = (unsigned)count_below(base | pc | (1u << bit), 0ull);
+                        if (m <= (unsigned)SD_WIN) {
+                            pc |= 1u << bit;
+                            if (m >= (unsigned)SD_WIN / 8) break;
+                        }
+                    }
+                    cut = max(base | pc, g0 + 1ull);
+                    break;
+                }
+                if (total <= (unsigned)SD_WIN || cut == tie) {
+                    // (bounded: a width that grew without limit could never be halved back)
+                    if (tid == 0 && total < (unsigned)SD_WIN / 8 && S.cut_w < 1048576.0f) S.cut_w *= 2.0f;
                     break;
                 }
                 if (tid == 0) S.cut_w *= 0.5f;

@@ -122,13 +122,21 @@ class Context:
         return mk.value, vg.value
 
     def last_stepdepth(self):
+        """Counters of the last metric / angular step depth (dmx_ctx_last_stepdepth*).  `batches` is the raw slot:
+        the batches of the batched search, or the queue refills of the serial one; `refills` is that slot when
+        the serial queue ran (0 for the batched search) and `attempts` its kernel launches (1 + retries with a
+        longer overflow list).  VGA metric / angular set expanders_popped, cells_relaxed and refills too, summed
+        over their sources (their kernel time is last_timing()'s)."""
         t, p, r = ctypes.c_double(), ctypes.c_int64(), ctypes.c_int64()
         N.check(N.lib().dmx_ctx_last_stepdepth(self.h, ctypes.byref(t), ctypes.byref(p), ctypes.byref(r)))
         d = np.zeros(4, dtype=np.int64)
         N.check(N.lib().dmx_ctx_last_stepdepth_detail(self.h, N.ptr(d)))
+        a = ctypes.c_int64()
+        N.check(N.lib().dmx_ctx_last_stepdepth_attempts(self.h, ctypes.byref(a)))
         return dict(seconds=t.value, expanders_popped=p.value, cells_relaxed=r.value,
                     mode=["serial", "batched", "batched-overflow-serial"][int(d[0])], batches=int(d[1]),
-                    improved=int(d[2]), ambiguous=int(d[3]))
+                    improved=int(d[2]), ambiguous=int(d[3]), refills=0 if int(d[0]) == 1 else int(d[1]),
+                    attempts=a.value)
 
     def last_isovist(self):
         """The last Graph.vga_isovist or Context.isovists (dmx_ctx_last_isovist): seconds of the host BSP build and

@@ -354,9 +354,19 @@ int dmx_visual_stepdepth(dmx_ctx* ctx, dmx_graph* g, const int32_t* sel_cells, i
 /* Kernel time of the last step-depth call, expanders popped, cells relaxed. */
 int dmx_ctx_last_stepdepth(dmx_ctx* ctx, double* seconds, int64_t* expanders_popped, int64_t* cells_relaxed);
 /* How the last metric step depth ran: out4 = {mode (0 serial, 1 batched over the whole GPU, 2 a
- * batch capacity overflowed and the serial kernel re-ran the search), batches (serial: queue
- * refills), cells improved, ambiguous cells folded sequentially}. */
+ * batch capacity overflowed and the serial kernel re-ran the search), batches, cells improved,
+ * ambiguous cells folded sequentially}.  The batches slot has two meanings.  Mode 1: the batches
+ * of the whole-GPU search.  Modes 0 and 2, angular step depth, and dmx_vga_metric /
+ * dmx_vga_angular (which leave mode 0; summed over their sources and attempts): the refills of the
+ * serial search's queue, i.e. how often its LDS window ran dry and was refilled from the HBM
+ * overflow list. */
 int dmx_ctx_last_stepdepth_detail(dmx_ctx* ctx, int64_t* out4);
+/* Kernel launches of the last serial metric / angular step depth: 1, plus one for every time the
+ * queue's overflow list was too small and the search ran again with a list four times as long (after
+ * four launches the call fails with DMX_ERR_CAPACITY).  0 when the batched search answered.  The
+ * environment variable DMX_SD_CAP sets the first list's length (a test hook, as for VGA metric /
+ * angular). */
+int dmx_ctx_last_stepdepth_attempts(dmx_ctx* ctx, int64_t* attempts);
 
 /* ---- .graph PointMap chunk (host) ------------------------------------------------------------ */
 /* The bytes PointMap::write emits into a .graph file (salalib/pointdata.cpp:1158-1188, with

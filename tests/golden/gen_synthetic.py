@@ -150,6 +150,28 @@ def make_plaza_map(W=1400, seed=14, origin=(0.0, 0.0), spacing=1.0):
     return region, lines, fill
 
 
+def make_pillar_hall(W, pitch, seg=0.3, seed=1):
+    """A [0, W]^2 hall with its four walls and one short "pillar" at every lattice point (i, j), i and j in
+    range(pitch, W - 1, pitch): a segment of length `seg` whose centre is the lattice point jittered by +-0.1 on
+    each axis and whose angle is uniform in [0, pi).  A pillar stays within 0.1 + seg / 2 of its lattice point,
+    inside that cell's neighbourhood, so a fill at spacing 1 from (1.5, 1.5) reaches every interior cell.  With
+    pitch 3 every filled cell is BLOCKED or next to a BLOCKED cell (an expander of the metric and angular
+    searches) while sight lines stay long, and the lattice makes distances tie all the time: the priority
+    queues of those searches grow to several times their LDS window.  Returns (region, lines [n][4], fill
+    point)."""
+    assert 0.1 + seg / 2 < 0.5, "a pillar must stay inside its lattice cell"
+    rng = np.random.default_rng(seed)
+    W = float(W)
+    lines = [[0.0, 0.0, W, 0.0], [W, 0.0, W, W], [W, W, 0.0, W], [0.0, W, 0.0, 0.0]]
+    for i in range(pitch, int(W) - 1, pitch):
+        for j in range(pitch, int(W) - 1, pitch):
+            cx, cy = (i, j) + rng.uniform(-0.1, 0.1, size=2)
+            a = rng.uniform(0.0, math.pi)
+            dx, dy = 0.5 * seg * math.cos(a), 0.5 * seg * math.sin(a)
+            lines.append([cx - dx, cy - dy, cx + dx, cy + dy])
+    return [0.0, 0.0, W, W], np.array(lines, dtype=np.float64), (1.5, 1.5)
+
+
 def write_csv(path, lines):
     with open(path, "w") as f:
         f.write("x1,y1,x2,y2\n")

@@ -798,8 +798,9 @@ def test_vga_metric_angular_overflow_rerun_is_exact(ctx, kind, monkeypatch):
     assert ctx.last_stats()["vga_fail_cells"] == 0
     monkeypatch.setenv("DMX_SD_CAP", "64")
     got = run()
-    if kind == "angular":   # cells seen at angle 0 are all queued: the 64-entry list overflows
-        assert ctx.last_stats()["vga_fail_cells"] > 0
+    # the 64-entry list overflows for both kinds (angular: the cells seen at angle 0 are all queued; metric:
+    # most sources queue more expanders than the window and the list hold -- 6684 re-runs when measured)
+    assert ctx.last_stats()["vga_fail_cells"] > 0
     np.testing.assert_array_equal(got.view(np.uint32), want.view(np.uint32))
 
 
