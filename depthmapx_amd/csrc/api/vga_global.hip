@@ -608,6 +608,11 @@ static int launch_tile(dmx_ctx* ctx, const VgaTileParams& Q, int64_t nsrc, size_
         else if (Q.pmask && !FG && nt > 32767) why = "narrow mask hint: tile index above 15 bits";
         else if (Q.asym_tiles && Q.alist_cap <= 0) why = "asymmetric mode without an A-cell list";
         if (why) return fail(DMX_ERR_STATE, (std::string("VGA tile launch: ") + why).c_str());
+        // the kernel's static LDS (TileShared, the work counters) comes on top of the dynamic part
+        hipFuncAttributes fa;
+        HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&vga_tile_kernel<NT, SPECIAL, RBM, FG>)));
+        if (fa.sharedSizeBytes + lds > (size_t)160 * 1024)
+            return fail(DMX_ERR_STATE, "VGA tile launch: static plus dynamic LDS above 160 KiB");
     }
     int occ = 0;
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, vga_tile_kernel<NT, SPECIAL, RBM, FG>, NT, lds));
@@ -615,7 +620,7 @@ static int launch_tile(dmx_ctx* ctx, const VgaTileParams& Q, int64_t nsrc, size_
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((int64_t)ctx->num_cu * occ, nsrc));
     const int64_t nt = (int64_t)Q.tw * Q.th;
     HIPCHK(xg.alloc((size_t)blocks * (FG ? 3 : 2) * nt));   // V, X [, F]
-    HIPCHK(queue.alloc((size_t)blocks * nt));
+    HIPCHK(queue.alloc((size_t)blocks * nt * 2));   // phase A's queue, then the row stage's (phase B in stages)
     HIPCHK(list.alloc((size_t)blocks * nt * 64 * 2));
     DevBuf<int32_t> tlist;   // per workgroup: the two unvisited-tile lists
     HIPCHK(tlist.alloc((size_t)blocks * nt * 2));
@@ -658,6 +663,7 @@ static int launch_tile(dmx_ctx* ctx, const VgaTileParams& Q, int64_t nsrc, size_
     // concurrent workgroups on neighbouring sources share L2 lines and hints
     P.chunk = std::max(1, policy::hook_int("DMX_VGA_CHUNK", policy::kVgaSourceChunk));
     P.nwork = (int)((P.src_end - P.src_begin + P.chunk - 1) / P.chunk);
+    P.bsplit = policy::hook_int("DMX_VGA_BSPLIT", policy::kVgaTileBSplit) & 3;
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     P.ctl = ctx->d_ctl;
     ctx->h_ctl->progress = 0;

@@ -31,6 +31,11 @@ constexpr int kVgaTileAlphaHbm = 1000;
 constexpr int kVgaTileCommonRuns = 4;
 // consecutive sources a workgroup takes per grab (neighbouring sources share L2 lines and hit hints)
 constexpr int kVgaSourceChunk = 1;
+// phase B of a bottom-up level in stages ("phase B in stages"): bit 0 tests the tile-to-tile
+// rows as a stage of its own, without the per-cell loads, and hands the tiles they leave to the cell stage; bit 1
+// lists the cells that miss their first heads and hints and tests their other runs a cell a lane.  0 is the fused
+// loop (a wave a tile through rows, cells and extension).  Hook: DMX_VGA_BSPLIT (0..3; A/B records, tests).
+constexpr int kVgaTileBSplit = 3;
 // ---- VGA global, direction-optimising fallback (vga_do.hip)
 constexpr int kVgaDoAlpha = 15;
 constexpr int kVgaDoShortList = 16;
