@@ -67,6 +67,7 @@ SIGNATURES = {
     "dmx_ctx_last_stepdepth": (_i32, [_vp, _vp, _vp, _vp]),
     "dmx_ctx_last_stepdepth_detail": (_i32, [_vp, _vp]),
     "dmx_ctx_last_stepdepth_attempts": (_i32, [_vp, _vp]),
+    "dmx_ctx_last_stepdepth_batched": (_i32, [_vp, _vp]),
     "dmx_ctx_last_phase_cycles": (_i32, [_vp, _vp]),
     "dmx_ctx_last_mk_reruns": (_i32, [_vp, _vp, ctypes.c_int64, _vp]),
     "dmx_chunk_write": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),

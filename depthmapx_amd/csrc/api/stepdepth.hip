@@ -27,7 +27,11 @@ static int stepdepth_batched(dmx_ctx* ctx, dmx_graph* g, const std::vector<uint8
         const size_t node = (size_t)(std::lower_bound(nc.begin(), nc.end(), c) - nc.begin());
         units += (nr[node] + SDB_UNIT - 1) / SDB_UNIT;
     }
-    const unsigned amb_cap = 1u << 16, ent_cap = 1u << 22;
+    // capacities of one batch (policy.hpp); the hooks only shrink them, to 1 at the least
+    const unsigned amb_cap =
+        (unsigned)std::min(policy::kSdbAmbCap, std::max(1, policy::hook_int("DMX_SDB_AMB_CAP", policy::kSdbAmbCap)));
+    const unsigned ent_cap =
+        (unsigned)std::min(policy::kSdbEntCap, std::max(1, policy::hook_int("DMX_SDB_ENT_CAP", policy::kSdbEntCap)));
     DevBuf<int32_t> d_ex, d_uown, d_win, d_ambid, d_touch, d_amb, d_ahead, d_enext;
     DevBuf<uint8_t> d_done;
     DevBuf<SdbExp> d_bq;
@@ -103,7 +107,8 @@ static int stepdepth_batched(dmx_ctx* ctx, dmx_graph* g, const std::vector<uint8
     }
     HIPCHK(hipEventRecord(ctx->ev1, s));
     HIPCHK(hipEventSynchronize(ctx->ev1));
-    if (hc.error) return 1;
+    // the attempt's counters are stored before an overflow gives it up: the serial fallback overwrites the
+    // time and last_sd_stats, the rest still says what the batched attempt met and why it stopped
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     ctx->last_sd_s = ms * 1e-3;
@@ -112,7 +117,12 @@ static int stepdepth_batched(dmx_ctx* ctx, dmx_graph* g, const std::vector<uint8
     ctx->last_sd_stats[2] = (long long)hc.batches;
     ctx->last_sd_extra[0] = (long long)hc.improved;
     ctx->last_sd_extra[1] = (long long)hc.ambiguous;
-    return DMX_OK;
+    ctx->last_sd_batched[0] = (long long)hc.fold_long;
+    ctx->last_sd_batched[1] = (long long)hc.list_max;
+    ctx->last_sd_batched[2] = (long long)hc.amb_max;
+    ctx->last_sd_batched[3] = (long long)hc.ent_max;
+    ctx->last_sd_batched[4] = (long long)hc.error;
+    return hc.error ? 1 : DMX_OK;
 }
 
 // STEPDEPTH -sdt metric (VGAMetricDepth) or, with ANG, -sdt angular (VGAAngularDepth): one search
@@ -180,6 +190,8 @@ static int stepdepth_impl(dmx_ctx* ctx, dmx_graph* g, const int32_t* sel_cells, 
     if (const char* e = getenv("DMX_SD_KERNEL")) batched = batched && strcmp(e, "serial") != 0;
     ctx->last_sd_mode = 0;
     ctx->last_sd_attempts = 0;
+    for (long long& v : ctx->last_sd_extra) v = 0;
+    for (long long& v : ctx->last_sd_batched) v = 0;
     if (batched) {
         int rc = stepdepth_batched(ctx, g, flags, sel, d_flags.p, d_sel.p, d_key.p, d_mdist.p, d_cum.p, d_last.p);
         if (rc < 0) return rc;
@@ -492,5 +504,11 @@ int dmx_ctx_last_stepdepth_detail(dmx_ctx* ctx, int64_t* out4) {
     out4[1] = ctx->last_sd_stats[2];
     out4[2] = ctx->last_sd_extra[0];
     out4[3] = ctx->last_sd_extra[1];
+    return DMX_OK;
+}
+
+int dmx_ctx_last_stepdepth_batched(dmx_ctx* ctx, int64_t* out5) {
+    if (!ctx || !out5) return fail(DMX_ERR_ARG, "bad arguments");
+    for (int i = 0; i < 5; i++) out5[i] = ctx->last_sd_batched[i];
     return DMX_OK;
 }

@@ -118,6 +118,7 @@ static int vga_search_all(dmx_ctx* ctx, dmx_graph* g, double radius, int gates_o
     ctx->last_sd_stats[1] = (long long)stv[1];
     ctx->last_sd_stats[2] = (long long)stv[2];   // queue refills, every source and attempt
     ctx->last_sd_mode = 0;                       // (the serial queue: the slot holds refills)
+    for (long long& v : ctx->last_sd_batched) v = 0;   // no batched search was tried
     ctx->last_stats[7] = se - sb;
     ctx->last_stats[8] = rerun;   // sources re-run with a larger overflow list
     return DMX_OK;

@@ -198,6 +198,9 @@ struct dmx_ctx {
     int last_sd_attempts = 0;                 // serial step depth: kernel launches (1 + overflow-list retries); batched: 0
     long long last_sd_extra[2] = {0, 0};      // batched: improved cells, ambiguous cells
     int last_sd_mode = 0;                     // 0 serial, 1 batched, 2 batched overflow -> serial
+    // batched attempt (kept through the serial fallback): cells folded by the block pass, longest relaxer
+    // list folded, most ambiguous cells / list entries of a batch, overflow reason bits (SDB_ERR_*)
+    long long last_sd_batched[5] = {0, 0, 0, 0, 0};
     long long phase_cycles[5] = {0, 0, 0, 0, 0};   // tile BFS: level 1, A, B, C, bookkeeping (sum over workgroups)
     DevBuf<int> counters;   // [0] work counter, [1] error word, [2..3] pool cursor (u64)
     DevBuf<unsigned long long> stats; // [0..1] makegraph, [4..6] vga

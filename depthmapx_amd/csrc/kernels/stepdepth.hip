@@ -417,8 +417,8 @@ __global__ void __launch_bounds__(SD_THREADS) stepdepth_kernel(StepDepthParams P
 // folded sequentially in pop order from the list of all their batch relaxers.  A batch is the
 // contiguous key range below the threshold, so batches run in the reference's pop order.
 // Kernels per batch: select -> relax<1> (min s) -> relax<2> (rivals) -> apply -> relax<3> (ambiguous
-// relaxer lists) -> fold -> finish.  Any capacity overflow raises ctl.error and the host re-runs the
-// search with the serial kernel.
+// relaxer lists) -> fold -> finish.  Any capacity overflow sets its reason bit in ctl.error and the host
+// re-runs the search with the serial kernel.
 constexpr int SDB_THREADS = 256;
 constexpr int SDB_UNIT = 256;          // runs of one expander per work unit (one workgroup)
 constexpr int SDB_FOLD_CAP = 2048;     // relaxers of one ambiguous cell in one batch
@@ -432,9 +432,16 @@ struct SdbExp {
 
 struct SdbCtl {
     unsigned long long gcur, gnext;   // smallest live expander key: this batch / the next one
-    unsigned nb, nunits, ntouch, namb, nent, done, error, batches;
+    unsigned nb, nunits, ntouch, namb, nent, done, error, batches;   // error: SDB_ERR_* reason bits
     unsigned long long relaxed, improved, ambiguous, popped;
+    // what the folds met (read by dmx_ctx_last_stepdepth_batched): cells folded by the block pass, the longest
+    // relaxer list of either pass, the most ambiguous cells and list entries of one batch (entries are counted
+    // past their capacity)
+    unsigned fold_long, list_max, amb_max, ent_max;
 };
+constexpr unsigned SDB_ERR_ENT = 1u;    // list entries of one batch (sdb_relax_kernel<3>)
+constexpr unsigned SDB_ERR_AMB = 2u;    // ambiguous cells of one batch (sdb_apply_kernel)
+constexpr unsigned SDB_ERR_FOLD = 4u;   // relaxers of one ambiguous cell (sdb_fold_kernel)
 
 struct SdbParams {
     int rows;
@@ -603,7 +610,7 @@ __global__ void __launch_bounds__(SDB_THREADS) sdb_relax_kernel(SdbParams P) {
                         P.ent[pos] = make_int2(a, b);
                         P.enext[pos] = atomicExch(&P.ahead[a], (int)pos);   // per-cell list: O(entries) fold
                     } else {
-                        C.error = 1;
+                        atomicOr(&C.error, SDB_ERR_ENT);
                     }
                 }
             }
@@ -654,7 +661,7 @@ __global__ void sdb_apply_kernel(SdbParams P) {
                 P.amb[a] = c;
                 P.ambid[c] = (int)a;
             } else {
-                C.error = 1;
+                atomicOr(&C.error, SDB_ERR_AMB);
             }
         }
     }
@@ -684,6 +691,7 @@ __global__ void __launch_bounds__(SDB_THREADS) sdb_fold_kernel(SdbParams P) {
             n++;
         }
         if (over) continue;   // long lists: the block pass below
+        atomicMax(&C.list_max, (unsigned)n);
         const int c = P.amb[a];
         const uint8_t f = P.flags[c];
         for (int i = 0; i < n; i++) sdb_update(P, C, c, c / P.rows, c % P.rows, f, P.bq[lp[i]]);
@@ -701,10 +709,12 @@ __global__ void __launch_bounds__(SDB_THREADS) sdb_fold_kernel(SdbParams P) {
             if (len <= 32) continue;
             int n = 0;
             for (int e = h; e >= 0; e = P.enext[e]) {
-                if (n == SDB_FOLD_CAP) { C.error = 1; n = -1; break; }
+                if (n == SDB_FOLD_CAP) { atomicOr(&C.error, SDB_ERR_FOLD); n = -1; break; }
                 lst[n++] = P.ent[e].y;
             }
             if (n >= 0) {
+                atomicAdd(&C.fold_long, 1u);
+                atomicMax(&C.list_max, (unsigned)n);
                 for (int i = 1; i < n; i++) {   // insertion sort by the relaxer's key (pop order)
                     const int v = lst[i];
                     const unsigned long long kv = P.bq[v].ku;
@@ -734,6 +744,8 @@ __global__ void sdb_finish_kernel(SdbParams P) {
     C.popped += C.nb;
     C.improved += C.ntouch;
     C.ambiguous += C.namb;
+    C.amb_max = max(C.amb_max, C.namb);
+    C.ent_max = max(C.ent_max, C.nent);
     C.gcur = C.gnext;
     C.gnext = SD_INF;
     C.nb = 0; C.nunits = 0; C.ntouch = 0; C.namb = 0; C.nent = 0;

@@ -40,6 +40,15 @@ constexpr int kVgaTileBSplit = 3;
 constexpr int kVgaDoAlpha = 15;
 constexpr int kVgaDoShortList = 16;
 
+// ---- batched metric step depth (sdb_* kernels, stepdepth.hip)
+// capacities of one batch: ambiguous cells (4 bytes each in `amb` and in `ahead`) and entries of their relaxer
+// lists (8 bytes in `ent`, 4 in `enext`: 48 MiB).  A batch that outgrows either gives the search to the serial
+// kernel.  Hooks: DMX_SDB_AMB_CAP, DMX_SDB_ENT_CAP (tests shrink them to the edge of a run; clamped to
+// [1, default]).  (The relaxers of one ambiguous cell, SDB_FOLD_CAP = 2048, size a static LDS array: a kernel
+// constant.)
+constexpr int kSdbAmbCap = 1 << 16;
+constexpr int kSdbEntCap = 1 << 22;
+
 // ---- VGA through vision (thruvision.hip)
 // side of the LDS window of 32-bit counters around the source (variant B; 0 would select variant A, global
 // atomics only).  64^2 x 4 B = 16 KiB lets eight workgroups share a CU's LDS (profiles/thruvision_ab.jsonl)

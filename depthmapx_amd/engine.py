@@ -126,17 +126,26 @@ class Context:
         the batches of the batched search, or the queue refills of the serial one; `refills` is that slot when
         the serial queue ran (0 for the batched search) and `attempts` its kernel launches (1 + retries with a
         longer overflow list).  VGA metric / angular set expanders_popped, cells_relaxed and refills too, summed
-        over their sources (their kernel time is last_timing()'s)."""
+        over their sources (their kernel time is last_timing()'s).  The batched search's folds
+        (dmx_ctx_last_stepdepth_batched): `fold_long` ambiguous cells folded by the one-block-per-cell pass,
+        `list_max` the longest relaxer list folded, `amb_max` / `ent_max` the most ambiguous cells / list entries
+        of one batch, and `overflow`: None, or the capacities a batch outgrew ("ent", "amb", "fold", joined by
+        "+").  In mode "batched-overflow-serial" these five, `improved` and `ambiguous` are the batched attempt's,
+        everything else the serial search's that replaced it."""
         t, p, r = ctypes.c_double(), ctypes.c_int64(), ctypes.c_int64()
         N.check(N.lib().dmx_ctx_last_stepdepth(self.h, ctypes.byref(t), ctypes.byref(p), ctypes.byref(r)))
         d = np.zeros(4, dtype=np.int64)
         N.check(N.lib().dmx_ctx_last_stepdepth_detail(self.h, N.ptr(d)))
         a = ctypes.c_int64()
         N.check(N.lib().dmx_ctx_last_stepdepth_attempts(self.h, ctypes.byref(a)))
+        b = np.zeros(5, dtype=np.int64)
+        N.check(N.lib().dmx_ctx_last_stepdepth_batched(self.h, N.ptr(b)))
+        why = "+".join(name for bit, name in ((1, "ent"), (2, "amb"), (4, "fold")) if int(b[4]) & bit)
         return dict(seconds=t.value, expanders_popped=p.value, cells_relaxed=r.value,
                     mode=["serial", "batched", "batched-overflow-serial"][int(d[0])], batches=int(d[1]),
                     improved=int(d[2]), ambiguous=int(d[3]), refills=0 if int(d[0]) == 1 else int(d[1]),
-                    attempts=a.value)
+                    attempts=a.value, fold_long=int(b[0]), list_max=int(b[1]), amb_max=int(b[2]),
+                    ent_max=int(b[3]), overflow=why or None)
 
     def last_isovist(self):
         """The last Graph.vga_isovist or Context.isovists (dmx_ctx_last_isovist): seconds of the host BSP build and

@@ -367,6 +367,16 @@ int dmx_ctx_last_stepdepth_detail(dmx_ctx* ctx, int64_t* out4);
  * environment variable DMX_SD_CAP sets the first list's length (a test hook, as for VGA metric /
  * angular). */
 int dmx_ctx_last_stepdepth_attempts(dmx_ctx* ctx, int64_t* attempts);
+/* What the folds of the last batched metric step depth met: out5 = {ambiguous cells folded by the
+ * one-block-per-cell pass (relaxer lists longer than 32), the longest relaxer list folded by either
+ * pass, the most ambiguous cells of one batch, the most relaxer-list entries of one batch (counted
+ * past their capacity), overflow reason bits}.  Reason bits: 1 the list entries of a batch (2^22), 2
+ * the ambiguous cells of a batch (2^16), 4 the relaxers of one ambiguous cell (2048); 0 when the
+ * batched search answered.  In mode 2 (dmx_ctx_last_stepdepth_detail) these are the counters of the
+ * batched attempt the serial kernel replaced, as are that call's cells improved and ambiguous cells;
+ * all zero when no batched search was tried.  The environment variables DMX_SDB_AMB_CAP and
+ * DMX_SDB_ENT_CAP shrink the two batch capacities (test hooks). */
+int dmx_ctx_last_stepdepth_batched(dmx_ctx* ctx, int64_t* out5);
 
 /* ---- .graph PointMap chunk (host) ------------------------------------------------------------ */
 /* The bytes PointMap::write emits into a .graph file (salalib/pointdata.cpp:1158-1188, with

@@ -172,6 +172,16 @@ def make_pillar_hall(W, pitch, seg=0.3, seed=1):
     return [0.0, 0.0, W, W], np.array(lines, dtype=np.float64), (1.5, 1.5)
 
 
+def make_open_room(W):
+    """A [0, W]^2 room: its four walls and nothing else.  A fill at spacing 1 from (1.5, 1.5) reaches the
+    (W - 1)^2 cells (1..W-1, 1..W-1), every one of which sees every other; the cells along the walls are the
+    only expanders of a metric or angular search besides its selection.  Returns (region, lines [4][4], fill
+    point)."""
+    W = float(W)
+    lines = [[0.0, 0.0, W, 0.0], [W, 0.0, W, W], [W, W, 0.0, W], [0.0, W, 0.0, 0.0]]
+    return [0.0, 0.0, W, W], np.array(lines, dtype=np.float64), (1.5, 1.5)
+
+
 def write_csv(path, lines):
     with open(path, "w") as f:
         f.write("x1,y1,x2,y2\n")
