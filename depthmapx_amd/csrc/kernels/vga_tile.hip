@@ -100,7 +100,8 @@ struct VgaTileParams {
     int bext;                 // phase-B runs after the heads (BEXT_DEFAULT)
     int crk;                  // tile-common runs tested in phase A (<= CRK)
     int bsplit;               // phase B in stages: bit 0 row stage + cell stage, bit 1 extension stage (0: fused)
-    const int2* mpairs;       // [nmp] merge links (cell a, cell b), x-major (Point::m_merge; nullptr: none)
+    int walk;                 // the tile walks take VGA_WALK_NF tiles a thread at once, level 1 is built in place (0: a tile at a time)
+    const int2* mpairs;      // [nmp] merge links (cell a, cell b), x-major (Point::m_merge; nullptr: none)
     int nmp;
     const int2* mamb;         // [nmamb] links with a context-filled odd end (that end first; merge_order_check)
     int nmamb;
@@ -126,6 +127,7 @@ struct VgaTileParams {
                                 // [14] tile-visibility rows read, [1] phase-C hits, [15] phase-C runs,
                                 // [16] phase-C hits certified by a fully seen frontier tile, [17] top-down clocks,
                                 // [18] phase-B tiles, [19] phase-B cells, [20] phase-B tiles resolved by ttvis, [25] pruned by ttany
+                                // [23] the longest tile list a level's walks took (a maximum, not a sum)
 };
 
 __device__ __forceinline__ int tile_id_of(int x, int y, int tw) {
@@ -239,6 +241,14 @@ static_assert(VGA_HINTS >= 2, "hint2 holds at least one slot");
                              // 3.150: profiles/vga_bstages_ab.txt)
 #endif
 static_assert(VGA_BB1 >= 1 && VGA_BB1 <= 64 && VGA_BB2 >= 1 && VGA_BB2 <= 64, "a batch entry a lane");
+#ifndef VGA_WALK_NF
+#define VGA_WALK_NF 4        // tile walks (phase A, level bookkeeping, X = F & ~V): tiles a thread whose loads are in flight
+                             // together (1000^2 VGA: 2 -> 3.087 s, 4 -> 3.060, 8 -> 4.093: the batch spills; parent 3.103)
+#endif
+static_assert(VGA_WALK_NF >= 1 && VGA_WALK_NF <= 8, "a walk batch is held in registers");
+#ifndef VGA_WALK_A
+#define VGA_WALK_A 1         // phase A's walk batched as well (1000^2 VGA: 0 -> 3.009 s, 1 -> 2.994; A's clocks -4 %)
+#endif
 #ifndef VGA_WIDE_PAIR
 #define VGA_WIDE_PAIR 1      // wide grids: the mask test takes two row-summary groups a round
 #endif
@@ -263,6 +273,12 @@ __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlan
 __device__ __forceinline__ long long uni64(unsigned long long v) {
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
     return (long long)(((unsigned long long)hi << 32) | lo);
+}
+// Set bits of a wave mask below this lane: a compacting append's slot.  (mbcnt needs no lane mask: the hoisted
+// (1 << lane) - 1 was a 64-bit value live through the whole kernel, reloaded from scratch inside phase B's appends
+// once the batched walks took its registers.)
+__device__ __forceinline__ int lanes_below(unsigned long long m) {
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
 // Tiles [t0, t1] of one summary line (bit per tile, one word per 64 tiles):
 // OR of F[base + tx * stride] & (cell mask of tile tx), 8 frontier tiles per round.
@@ -778,6 +794,29 @@ __device__ __forceinline__ bool pmask_hit_wide(const VgaTileParams& P, const uns
     return false;
 }
 
+// X = F & ~V over all tiles after a top-down push (and after level 1 of a source that is not plain), NF tiles a
+// thread at once: the loads of a batch are issued before the first is used.  X is zero before (vga_tile_kernel,
+// "X being all zero"), so only the non-zero words are stored.
+template <int NT, int NF>
+__device__ __forceinline__ void x_from_f(const unsigned long long* F, const unsigned long long* Vg,
+                                         unsigned long long* Xg, int nt, int tid) {
+    for (int t0 = 0; t0 < nt; t0 += NF * NT) {
+        unsigned long long f[NF], v[NF];
+#pragma unroll
+        for (int k = 0; k < NF; k++) {
+            const int tc = min(t0 + k * NT + tid, nt - 1);
+            f[k] = F[tc];
+            v[k] = Vg[tc];
+        }
+#pragma unroll
+        for (int k = 0; k < NF; k++) {
+            const int t = t0 + k * NT + tid;
+            const unsigned long long x = f[k] & ~v[k];
+            if (t < nt && x) Xg[t] = x;
+        }
+    }
+}
+
 // V (visited) and X (next level) are per-workgroup bitmaps in HBM (they stay in the L2/MALL; a
 // source touches each word a few times), F (frontier, read by every run test) is in LDS.
 // SPECIAL = false: the graph has no asymmetric nodes (every U_f cell is regular), no exact path.
@@ -828,6 +867,16 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
         S.mpart = -1; S.mcorr = 0; S.mdisc = 0;
         S.an = 0; S.aitem = 0;
     }
+    // The batched walks (P.walk, DESIGN.md section 2 "tile walks") rely on X being all zero between sources, so that
+    // a plain source need not clear it and a level stores only its non-zero words.  Established here, once a
+    // workgroup a launch (the barrier of the first grab orders it); kept by the level bookkeeping, which clears
+    // every word of X it finds set -- X only ever holds unvisited cells, whose tiles the walk lists -- and which
+    // every exit of the level loop follows: the radius and target tests at its top, cnt == 0 and the level overflow
+    // after it.  A cancelled launch stops between sources.
+    const bool walk = P.walk != 0;
+    constexpr int WNF = VGA_WALK_NF;
+    if (walk)
+        for (int t = tid; t < nt; t += NT) Xg[t] = 0ull;
     int64_t chunk_end = 0;
     int64_t src = -1;
     for (;;) {
@@ -854,10 +903,35 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
         }
         const int stile = (sy >> 3) * tw + (sx >> 3);
         const unsigned long long sbit = 1ull << ((sy & 7) * 8 + (sx & 7));
-        for (int t = tid; t < nt; t += NT) {
-            Vg[t] = P.seed_tiles[t] | (t == stile ? sbit : 0ull);
-            Xg[t] = 0ull;
-            F[t] = 0ull;
+        // A plain source -- no seeds, a map without merge links, F in LDS, not the asymmetric mode -- builds its
+        // level 1 in place: V at level 0 is seed_tiles | source bit, so the first bookkeeping forms X from F and
+        // that, writes V once and X never.  Its setup clears F alone (X is zero between sources, above).  Seeded
+        // searches, maps with merge links (a partner's level-0 bit is ORed into V), the asymmetric mode and the
+        // HBM frontier keep V and X initialised here and level 1 written to X.
+        const bool plain = walk && !FG && !seeded && !P.nmp && !P.asym_tiles;
+        if (plain) {
+            for (int t = tid; t < nt; t += NT) F[t] = 0ull;
+        } else if (walk) {
+            for (int t0 = 0; t0 < nt; t0 += WNF * NT) {
+                unsigned long long sd[WNF];
+#pragma unroll
+                for (int k = 0; k < WNF; k++) sd[k] = P.seed_tiles[min(t0 + k * NT + tid, nt - 1)];
+#pragma unroll
+                for (int k = 0; k < WNF; k++) {
+                    const int t = t0 + k * NT + tid;
+                    if (t < nt) {
+                        Vg[t] = sd[k] | (t == stile ? sbit : 0ull);
+                        Xg[t] = 0ull;
+                        F[t] = 0ull;
+                    }
+                }
+            }
+        } else {
+            for (int t = tid; t < nt; t += NT) {
+                Vg[t] = P.seed_tiles[t] | (t == stile ? sbit : 0ull);
+                Xg[t] = 0ull;
+                F[t] = 0ull;
+            }
         }
         for (int i = tid; i < VGA_HMAX; i += NT) hist[i] = 0;
         long long n_in_uf = (P.seed_tiles[stile] & sbit) ? 0 : 1;
@@ -930,13 +1004,79 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                     if (tid < nr) rt += (unsigned)((nr - tid + NT - 1) / NT);
                 }
                 sync_global();
-                for (int t = tid; t < nt; t += NT) Xg[t] = F[t] & ~Vg[t];
+                // (a plain source: the bookkeeping below forms X from F and the closed-form V)
+                if (!plain) {
+                    if (walk) x_from_f<NT, WNF>(F, Vg, Xg, nt, tid);
+                    else
+                        for (int t = tid; t < nt; t += NT) Xg[t] = F[t] & ~Vg[t];
+                }
                 if (tid == 0) { const unsigned long long n = __builtin_amdgcn_s_memtime(); ST(8, n - tmark); tmark = n; }
             } else if (bottom_up) {
                 // ---- A: tile-common runs
                 // only the tiles the previous level's bookkeeping listed can hold an unvisited cell
                 const int32_t* TLc = TL + (level & 1) * nt;
                 const int ntl = uni(S.tn[level & 1]);
+                // P.walk: WNF list entries a thread at once -- their list loads, then the common runs, V, the regular
+                // mask and the asymmetric mode's candidates of all of them, are in flight before the first test; one
+                // queue append a wave a batch.  The tests are those of the loop below.
+                if (walk && VGA_WALK_A)
+                for (int i0 = 0; i0 < ntl; i0 += WNF * NT) {
+                    static_assert(CRK == 4, "phase A keeps the common runs in four words");
+                    int tt[WNF];
+#pragma unroll
+                    for (int k = 0; k < WNF; k++) tt[k] = TLc[min(i0 + k * NT + tid, ntl - 1)];
+                    unsigned long long cw[WNF][CRK], vv[WNF], rg[WNF], au[WNF], UU[WNF];
+#pragma unroll
+                    for (int k = 0; k < WNF; k++) {
+                        const int t = tt[k];
+#pragma unroll
+                        for (int j = 0; j < CRK; j++) cw[k][j] = run_word(P.cr + CRK * t + j);
+                        vv[k] = Vg[t];
+                        rg[k] = P.regular_tiles[t];
+                        au[k] = P.asym_tiles ? P.asym_uf[t] : ~0ull;
+                    }
+#pragma unroll
+                    for (int k = 0; k < WNF; k++) {
+                        const int t = tt[k];
+                        unsigned long long U = i0 + k * NT + tid < ntl ? ~vv[k] & au[k] : 0ull;
+                        const unsigned long long R = U & rg[k];
+                        if (R) {
+                            bool hit = false;
+#pragma unroll 1
+                            for (int j = 0; j < CRK; j++) {
+                                const Run cj = run_of(j == 0 ? cw[k][0] : j == 1 ? cw[k][1] : j == 2 ? cw[k][2] : cw[k][3]);
+                                if (!hit && j < P.crk && cj.x0 >= 0) {
+                                    rt++;
+                                    hit = run_hits_fs(FV, cj);
+                                }
+                            }
+                            if (hit) { Xg[t] = R; U &= ~R; ST(7, 1); }
+                        }
+                        UU[k] = U;
+                    }
+                    unsigned long long want[WNF];
+                    int tot = 0;
+#pragma unroll
+                    for (int k = 0; k < WNF; k++) {
+                        want[k] = __ballot(UU[k] != 0ull);
+                        tot += __popcll(want[k]);
+                    }
+                    if (tot) {
+                        int base = 0;
+                        if (lane == 0) base = atomicAdd(&S.qn, tot);
+                        base = __shfl(base, 0);
+#pragma unroll
+                        for (int k = 0; k < WNF; k++) {
+                            if (UU[k]) {
+                                const int pos = base + lanes_below(want[k]);
+                                Q[pos] = make_int4(tt[k], (UU[k] & ~rg[k]) ? 1 : 0, (int)(unsigned)(UU[k] & 0xFFFFFFFFull),
+                                                   (int)(unsigned)(UU[k] >> 32));
+                            }
+                            base += __popcll(want[k]);
+                        }
+                    }
+                }
+                else
                 for (int t0 = 0; t0 < ntl; t0 += NT) {
                     const int t = t0 + tid < ntl ? TLc[t0 + tid] : nt;
                     unsigned long long U = 0ull, rg = ~0ull;
@@ -974,7 +1114,7 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                         if (lane == 0) base = atomicAdd(&S.qn, __popcll(want));
                         base = __shfl(base, 0);
                         if (U) {
-                            const int pos = base + __popcll(want & ((1ull << lane) - 1ull));
+                            const int pos = base + lanes_below(want);
                             // .y: the tile still holds an asymmetric cell (phase B then loads the regular mask)
                             Q[pos] = make_int4(t, (U & ~rg) ? 1 : 0, (int)(unsigned)(U & 0xFFFFFFFFull),
                                                (int)(unsigned)(U >> 32));
@@ -1100,7 +1240,7 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                             if (lane == 0) base = atomicAdd(&S.q2n, __popcll(kb));
                             base = __shfl(base, 0);
                             if (keep)
-                                Q2[base + __popcll(kb & ((1ull << lane) - 1ull))] =
+                                Q2[base + lanes_below(kb)] =
                                     make_int4(ev.x, ev.y, (int)(unsigned)(keep & 0xFFFFFFFFull), (int)(unsigned)(keep >> 32));
                         }
                     }
@@ -1273,14 +1413,14 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                         int base = 0;
                         if (lane == 0) base = atomicAdd(&S.hn, __popcll(hw));
                         base = __shfl(base, 0);
-                        if (to_hard) L[base + __popcll(hw & ((1ull << lane) - 1ull))] = hard_val;
+                        if (to_hard) L[base + lanes_below(hw)] = hard_val;
                     }
                     const unsigned long long xw = __ballot(to_ext);
                     if (xw) {
                         int base = 0;
                         if (lane == 0) base = atomicAdd(&S.en, __popcll(xw));
                         base = __shfl(base, 0);
-                        if (to_ext) EL[base + __popcll(xw & ((1ull << lane) - 1ull))] = id;
+                        if (to_ext) EL[base + lanes_below(xw)] = id;
                     }
                 }
                 if (ext_stage) {
@@ -1339,7 +1479,7 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                             int base = 0;
                             if (lane == 0) base = atomicAdd(&S.hn, __popcll(hw));
                             base = __shfl(base, 0);
-                            if (to_hard) L[base + __popcll(hw & ((1ull << lane) - 1ull))] = id;
+                            if (to_hard) L[base + lanes_below(hw)] = id;
                         }
                     }
                 }
@@ -1585,7 +1725,9 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                     if (lane == 0) rt += (unsigned)nr;
                 }
                 sync_global();
-                for (int t = tid; t < nt; t += NT) Xg[t] = F[t] & ~Vg[t];
+                if (walk) x_from_f<NT, WNF>(F, Vg, Xg, nt, tid);
+                else
+                    for (int t = tid; t < nt; t += NT) Xg[t] = F[t] & ~Vg[t];
             }
             sync_global();
             if (P.asym_tiles) {
@@ -1657,6 +1799,94 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
             const int32_t* TLc = TL + (level & 1) * nt;
             int32_t* TLn = TL + ((level + 1) & 1) * nt;
             const int nwalk = have_list ? uni(S.tn[level & 1]) : nt;
+            if (tid == 0 && have_list) atomicMax(&SC[23], (unsigned long long)nwalk);   // (vga_tl_max)
+            // P.walk: WNF tiles a thread at once -- the list entries, then X and V of all of them (a plain source's
+            // first level: the seed masks, with X formed from F in place) in flight before the first tile's work; one
+            // list append a wave a batch.  The work a tile is that of the loop below (the masks of the unexpanded and of
+            // the asymmetric cells are still loaded a tile at a time, under a radius and in the asymmetric mode only).
+            const bool fused0 = plain && !have_list;
+            const bool nonexp = P.radius != -1 || seeded;
+            if (walk)
+            for (int i0 = 0; i0 < nwalk; i0 += WNF * NT) {
+                // (the uniform choices stand around whole batches, so that a batch's loads share a basic block)
+                int tt[WNF];
+                if (have_list) {
+#pragma unroll
+                    for (int k = 0; k < WNF; k++) tt[k] = TLc[min(i0 + k * NT + tid, nwalk - 1)];
+                } else {
+#pragma unroll
+                    for (int k = 0; k < WNF; k++) tt[k] = min(i0 + k * NT + tid, nwalk - 1);
+                }
+                unsigned long long xx[WNF], vv[WNF];
+                if (fused0) {
+#pragma unroll
+                    for (int k = 0; k < WNF; k++) {
+                        xx[k] = 0ull;
+                        vv[k] = P.seed_tiles[tt[k]];   // (the source's bit joins below: a use here would wait for the load)
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < WNF; k++) {
+                        xx[k] = ld_wg(&Xg[tt[k]]);
+                        vv[k] = Vg[tt[k]];
+                    }
+                }
+                bool open[WNF];
+#pragma unroll
+                for (int k = 0; k < WNF; k++) {
+                    const int t = tt[k];
+                    open[k] = false;
+                    if (i0 + k * NT + tid < nwalk) {
+                        const unsigned long long v0 = vv[k] | (fused0 && t == stile ? sbit : 0ull);
+                        unsigned long long x = fused0 ? F[t] & ~v0 : xx[k];
+                        open[k] = ~(v0 | x) != 0ull;
+                        if (fused0) Vg[t] = v0 | x;   // (V's first and only initialisation for this source)
+                        if (x) {
+                            c_loc += (unsigned long long)__popcll(x);
+                            if (!fused0) {
+                                Vg[t] = v0 | x;
+                                Xg[t] = 0ull;
+                            }
+                            if (P.cell_level)
+                                for (unsigned long long m = x; m; m &= m - 1) P.cell_level[t * 64 + __ffsll((long long)m) - 1] = level + 1;
+                            if (nonexp) x &= ~P.nonexp_tiles[t];
+                            m_loc += (unsigned long long)__popcll(x);
+                            unsigned long long xa = P.asym_tiles ? x & P.asym_tiles[t] : 0ull;
+                            if (xa) {
+                                x &= ~xa;
+                                int pos = atomicAdd(&S.an, __popcll(xa));
+                                int32_t* AL = P.alist + (size_t)blockIdx.x * P.alist_cap;
+                                for (; xa; xa &= xa - 1)
+                                    if (pos < P.alist_cap) AL[pos++] = (t << 6) | (__ffsll((long long)xa) - 1);
+                            }
+                            if (x) {
+                                const int tx = t % tw, ty = t / tw;
+                                atomicOr(&Fsr[ty * wr + (tx >> 6)], 1ull << (tx & 63));
+                                if (!RBM) atomicOr(&Fsc[tx * wc + (ty >> 6)], 1ull << (ty & 63));
+                            }
+                        }
+                        F[t] = x;
+                    }
+                }
+                unsigned long long om[WNF];
+                int tot = 0;
+#pragma unroll
+                for (int k = 0; k < WNF; k++) {
+                    om[k] = __ballot(open[k]);
+                    tot += __popcll(om[k]);
+                }
+                if (tot) {
+                    int base = 0;
+                    if (lane == 0) base = atomicAdd(&S.tn[(level + 1) & 1], tot);
+                    base = __shfl(base, 0);
+#pragma unroll
+                    for (int k = 0; k < WNF; k++) {
+                        if (open[k]) TLn[base + lanes_below(om[k])] = tt[k];
+                        base += __popcll(om[k]);
+                    }
+                }
+            }
+            else
             for (int i0 = 0; i0 < nwalk; i0 += NT) {
                 const int t = i0 + tid < nwalk ? (have_list ? TLc[i0 + tid] : i0 + tid) : -1;
                 bool open = false;
@@ -1697,7 +1927,7 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                     int base = 0;
                     if (lane == 0) base = atomicAdd(&S.tn[(level + 1) & 1], __popcll(om));
                     base = __shfl(base, 0);
-                    if (open) TLn[base + __popcll(om & ((1ull << lane) - 1ull))] = t;
+                    if (open) TLn[base + lanes_below(om)] = t;
                 }
             }
             for (int off = 32; off >= 1; off >>= 1) {
@@ -1803,7 +2033,10 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
     if (lane == 0 && nlt) ST(30, nlt);
     __syncthreads();
     for (int i = tid; i < 32; i += NT)
-        if (SC[i]) atomicAdd(&P.stats[i], SC[i]);
+        if (SC[i]) {
+            if (i == 23) atomicMax(&P.stats[i], SC[i]);   // the longest tile list: a maximum, not a sum
+            else atomicAdd(&P.stats[i], SC[i]);
+        }
 #undef ST
 }
 

@@ -36,6 +36,11 @@ constexpr int kVgaSourceChunk = 1;
 // lists the cells that miss their first heads and hints and tests their other runs a cell a lane.  0 is the fused
 // loop (a wave a tile through rows, cells and extension).  Hook: DMX_VGA_BSPLIT (0..3; A/B records, tests).
 constexpr int kVgaTileBSplit = 3;
+// the tile walks of a level (phase A, the level bookkeeping, X = F & ~V) take VGA_WALK_NF tiles a thread at once, all
+// their loads in flight before the first is used, and a plain source builds its level 1 in place (DESIGN.md section 2,
+// "tile walks").  0 selects the loops that take a tile at a time.  A correctness switch for tests and bisecting, not
+// a tuning knob: timings are taken against the parent build.  Hook: DMX_VGA_WALK (0 / 1).
+constexpr int kVgaTileWalk = 1;
 // ---- VGA global, direction-optimising fallback (vga_do.hip)
 constexpr int kVgaDoAlpha = 15;
 constexpr int kVgaDoShortList = 16;
