@@ -53,6 +53,9 @@ SIGNATURES = {
     "dmx_graph_set_prep_shard": (_i32, [_vp, _i64, _i64, _vp, _vp]),
     "dmx_vga_local": (_i32, [_vp, _vp, _i32, _i64, _i64, _vp]),
     "dmx_vga_thruvision": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp]),
+    "dmx_graph_connections": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp]),
+    "dmx_graph_connections_csv": (_i32, [_vp, _vp, _i64, _i64, _cs, _vp, _vp, _i64, _vp]),
+    "dmx_ctx_last_connections": (_i32, [_vp, _vp, _vp, _vp]),
     "dmx_vga_isovist": (_i32, [_vp, _vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "dmx_ctx_last_isovist": (_i32, [_vp, _vp, _vp, _vp]),
     "dmx_isovists": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
@@ -83,6 +86,8 @@ SIGNATURES = {
     "dmx_graph_set_drawing": (_i32, [_vp, _vp, _i64]),
     "dmx_pointmap_set_merges": (_i32, [_vp, _vp, _i64]),
     "dmx_chunk_merges": (_i32, [_vp, _vp, _vp]),
+    "dmx_chunk_rows": (_i32, [_vp, _vp, _vp]),
+    "dmx_chunk_merge_records": (_i32, [_vp, _vp, _vp]),
     "dmx_chunk_flags": (_i32, [_vp, _vp, _vp, _vp, _vp]),
     "dmx_chunk_set_column": (_i32, [_vp, _cs, _vp, _vp, _i32, _i32]),
     "dmx_chunk_set_displayed": (_i32, [_vp, _i32]),

@@ -233,6 +233,34 @@ int dmx_chunk_merges(const dmx_chunk* c, int32_t* cell_pairs, int64_t* n) {
     return DMX_OK;
 }
 
+// The attribute rows in key order, and which of them the map's layers show (isObjectVisible, layermanager.h:84-87:
+// LayerManagerImpl::m_visibleLayers & the row's layer key; m_visibleLayers is the second int64 the layer block
+// stores, layermanagerimpl.cpp:90-105).
+int dmx_chunk_rows(const dmx_chunk* c, int32_t* keys, uint8_t* visible) {
+    if (!c) return fail(DMX_ERR_ARG, "chunk is NULL");
+    const ParsedChunk& p = c->pc;
+    int64_t shown = 1;   // a fresh LayerManagerImpl: "Everything" visible
+    if (p.layers_raw.size() >= 16) std::memcpy(&shown, p.layers_raw.data() + 8, 8);
+    for (size_t i = 0; i < p.row_keys.size(); i++) {
+        if (keys) keys[i] = p.row_keys[i];
+        if (visible) visible[i] = ((i < p.row_layers.size() ? p.row_layers[i] : 1) & shown) != 0;
+    }
+    return DMX_OK;
+}
+
+// Point::m_merge as stored: (cell, partner cell) of every point with a link, in x-major order of the cell.
+int dmx_chunk_merge_records(const dmx_chunk* c, int32_t* cell_pairs, int64_t* n) {
+    if (!c || !n) return fail(DMX_ERR_ARG, "bad arguments");
+    const ParsedChunk& p = c->pc;
+    const int64_t m = (int64_t)p.merge_pairs.size() / 2;
+    if (cell_pairs) {
+        if (*n < m) return fail(DMX_ERR_ARG, "buffer too small");
+        if (m) std::memcpy(cell_pairs, p.merge_pairs.data(), p.merge_pairs.size() * 4);
+    }
+    *n = m;
+    return DMX_OK;
+}
+
 // The isovist analysis's per-node data a parsed chunk stores (Bin::m_occ_distance, Node::m_occlusion_bins).
 int dmx_chunk_occlusion(const dmx_chunk* c, float* occ_dist, int32_t* occ_counts, int32_t* occ_pixels, int64_t cap,
                         int64_t* total) {

@@ -1,12 +1,15 @@
 // dmxcli -- command-line front-end of the MI355X engine with the depthmapXcli mode-parser surface
-// for the accelerated path: VISPREP (grid, fill, makeGraph), VGA (-vm visibility -vg -vr) and
-// STEPDEPTH (-sdt metric, -sdt visual).  Flags, validation messages, the "-t" timing CSV and the exit status
+// for the accelerated path: VISPREP (grid, fill, makeGraph), VGA (-vm visibility -vg -vr),
+// STEPDEPTH (-sdt metric, -sdt visual) and EXPORT (-em pointmap-data-csv, pointmap-connections-csv,
+// pointmap-links-csv).  Flags, validation messages, the "-t" timing CSV and the exit status
 // follow the reference CLI:
 //   depthmapXcli/main.cpp:22-54, commandlineparser.cpp:51-142, visprepparser.cpp:26-172,
 //   vgaparser.cpp:29-106, radiusconverter.cpp:24-61, stepdepthparser.cpp:26-100,
 //   runmethods.cpp:33-45 (loadGraph), :227-267 (runVga), :279-341 (runVisualPrep),
-//   :735-778 (runStepDepth), performancewriter.cpp:60-76, salalib/gridproperties.cpp:4-13.
-// Host code over the C ABI (include/dmx.h); every analysis runs on the GPU.
+//   :735-778 (runStepDepth), exportparser.cpp:25-80, runmethods.cpp:649-733 (exportData),
+//   performancewriter.cpp:60-76, salalib/gridproperties.cpp:4-13.
+// Host code over the C ABI (include/dmx.h); every analysis runs on the GPU (the data and links exports are host
+// code and open no GPU).
 //
 // Files: a depthmapX .graph (MetaGraph::readFromFile / write, mgraph.cpp:2475-2757, through
 // dmx_graphfile_*), written back as .graph; or a drawing as a CSV of lines (header x1,y1,x2,y2; what
@@ -28,6 +31,7 @@
 #include <vector>
 
 #include "../../../include/dmx.h"
+#include "../policy.hpp"
 
 namespace {
 
@@ -867,12 +871,192 @@ struct StepDepth : Mode {
     }
 };
 
+// ExportParser (exportparser.cpp:25-80) + exportData (runmethods.cpp:649-733) for the displayed point map.
+// pointmap-data-csv and pointmap-links-csv are host code over the parsed chunk and never open the GPU;
+// pointmap-connections-csv expands the graph on the GPU (dmx_graph_connections_csv) in node ranges of a fixed
+// text budget (policy::kConnTextBudget).  The shapegraph-* modes parse and are refused when run.
+struct Export : Mode {
+    enum { NONE, POINTMAP_DATA_CSV, POINTMAP_CONNECTIONS_CSV, POINTMAP_LINKS_CSV, SHAPEGRAPH } mode = NONE;
+    std::string mode_name;
+    std::string name() const override { return "EXPORT"; }
+    void parse(int argc, char** argv) override {
+        for (int i = 1; i < argc;) {
+            if (!std::strcmp("-em", argv[i])) {
+                if (mode != NONE) throw CommandLineException("-em can only be used once, modes are mutually exclusive");
+                enforce_argument("-em", i, argc, argv);
+                mode_name = argv[i];
+                if (mode_name == "pointmap-data-csv") mode = POINTMAP_DATA_CSV;
+                else if (mode_name == "pointmap-connections-csv") mode = POINTMAP_CONNECTIONS_CSV;
+                else if (mode_name == "pointmap-links-csv") mode = POINTMAP_LINKS_CSV;
+                else if (mode_name == "shapegraph-map-csv" || mode_name == "shapegraph-map-mif" ||
+                         mode_name == "shapegraph-connections-csv" || mode_name == "shapegraph-links-unlinks-csv")
+                    mode = SHAPEGRAPH;
+                else throw CommandLineException(std::string("Invalid EXPORT mode: ") + argv[i]);
+            }
+            ++i;
+        }
+    }
+    // PixelRef::operator int (salalib/pixelref.h:81-82) of an x-major cell
+    static int pixel_ref(int32_t cell, int32_t rows) { return ((cell / rows) << 16) + ((cell % rows) & 0xffff); }
+    static void put(std::string& s, double v) {   // ostream << with precision(8), default float format
+        char b[40];
+        s.append(b, (size_t)snprintf(b, sizeof(b), "%.8g", v));
+    }
+    static void write_file(const std::string& path, const std::string& text) {
+        std::ofstream f(path, std::ios::binary | std::ios::trunc);
+        f.write(text.data(), (std::streamsize)text.size());
+        if (!f) throw RuntimeException("Failed to write " + path);
+    }
+    // PointMap::outputSummary(stream, ',') (pointdata.cpp:554-587)
+    static std::string data_csv(const dmx_chunk* ch) {
+        int32_t ncols = 0;
+        double spacing = 0, bl[2] = {0, 0};
+        check(dmx_chunk_info(ch, nullptr, nullptr, &spacing, bl, nullptr, nullptr, &ncols, nullptr, nullptr));
+        int64_t nrows = 0;
+        check(dmx_chunk_flags(ch, nullptr, nullptr, nullptr, &nrows));
+        std::vector<std::string> names((size_t)ncols);
+        std::vector<std::vector<float>> vals((size_t)ncols, std::vector<float>((size_t)nrows));
+        for (int i = 0; i < ncols; i++) {
+            char nm[1024] = {0};
+            check(dmx_chunk_column(ch, i, nm, (int)sizeof(nm), vals[i].data(), nullptr));
+            names[i] = nm;
+        }
+        std::vector<int> order((size_t)ncols);
+        for (int i = 0; i < ncols; i++) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](int a, int b) { return names[a] < names[b]; });
+        std::vector<int32_t> keys((size_t)nrows);
+        std::vector<uint8_t> visible((size_t)nrows);
+        check(dmx_chunk_rows(ch, keys.data(), visible.data()));
+        std::string s = "Ref,x,y";
+        for (int i : order) s += "," + names[i];
+        s += "\n";
+        for (int64_t r = 0; r < nrows; r++) {
+            if (!visible[r]) continue;   // isObjectVisible(m_layers, row)
+            const int key = keys[r];
+            const short x = (short)(key >> 16), y = (short)(key & 0xffff);
+            s += std::to_string(key);
+            s += ",";
+            put(s, bl[0] + spacing * 1.0 * double(x));   // PointMap::depixelate (pointdata.h:353-357)
+            s += ",";
+            put(s, bl[1] + spacing * 1.0 * double(y));
+            for (int i : order) {
+                s += ",";
+                put(s, (double)vals[i][r]);
+            }
+            s += "\n";
+        }
+        return s;
+    }
+    // PointMap::outputLinksAsCSV(stream, ",") (pointdata.cpp:683-706): a point counts when it is filled() and has
+    // its node (a processed map's filled points)
+    static std::string links_csv(const dmx_chunk* ch) {
+        int32_t cols = 0, rows = 0;
+        check(dmx_chunk_info(ch, &cols, &rows, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+        int processed = 0;
+        check(dmx_chunk_flags(ch, &processed, nullptr, nullptr, nullptr));
+        std::vector<int32_t> st((size_t)cols * rows);
+        check(dmx_chunk_arrays(ch, st.data(), nullptr, nullptr, nullptr));
+        int64_t n = 0;
+        check(dmx_chunk_merge_records(ch, nullptr, &n));
+        std::vector<int32_t> rec((size_t)n * 2);
+        if (n) check(dmx_chunk_merge_records(ch, rec.data(), &n));
+        std::vector<std::pair<int32_t, int32_t>> recs;
+        for (int64_t i = 0; i < n; i++) recs.emplace_back(rec[2 * i], rec[2 * i + 1]);
+        std::stable_sort(recs.begin(), recs.end(), [](auto& a, auto& b) { return a.first < b.first; });
+        std::string s = "RefFrom,RefTo";
+        std::vector<uint8_t> seen(st.size(), 0);
+        for (auto& r : recs) {
+            if (!processed || !(st[r.first] & 0x2)) continue;   // Point::FILLED
+            if (seen[r.first]) continue;
+            seen[r.first] = 1;
+            if (r.second >= 0 && (size_t)r.second < seen.size()) seen[r.second] = 1;
+            s += "\n" + std::to_string(pixel_ref(r.first, rows)) + "," + std::to_string(pixel_ref(r.second, rows));
+        }
+        return s;
+    }
+    void run(const Args& a, Perf& perf) override {
+        Document d;
+        const auto t0 = std::chrono::steady_clock::now();
+        read_document(a.file, d);
+        double load_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        // exportData's switch (runmethods.cpp:653-732): without -em the mode is NONE and the default branch throws,
+        // after the graph was loaded
+        if (mode == NONE) throw RuntimeException("Error, unsupported export mode");
+        if (mode == SHAPEGRAPH)
+            throw RuntimeException("Export mode " + mode_name + " needs a shape graph: only the pointmap-* export modes "
+                                   "are part of the accelerated path");
+        if (!d.any_map()) throw RuntimeException("No map exists to use. Please create a new one by providing a grid size");
+        const std::vector<uint8_t> bytes = d.displayed_chunk();
+        if (mode != POINTMAP_CONNECTIONS_CSV) {
+            dmx_chunk* ch = nullptr;
+            const auto t1 = std::chrono::steady_clock::now();
+            check(dmx_chunk_parse(bytes.data(), (int64_t)bytes.size(), &ch));
+            std::unique_ptr<dmx_chunk, int (*)(dmx_chunk*)> guard(ch, dmx_chunk_free);
+            perf.add("Load graph file", load_s + std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count());
+            // the reference's action name for the links is the connections' (runmethods.cpp:674)
+            timed(perf, mode == POINTMAP_DATA_CSV ? "Writing pointmap data" : "Writing pointmap connections",
+                  [&] { write_file(a.out, mode == POINTMAP_DATA_CSV ? data_csv(ch) : links_csv(ch)); });
+            return;
+        }
+        const std::string header = "RefFrom,RefTo";
+        std::unique_ptr<Context> Cp;   // outlives the map's graph
+        LoadedMap m;
+        const auto t2 = std::chrono::steady_clock::now();
+        check(dmx_chunk_parse(bytes.data(), (int64_t)bytes.size(), &m.chunk));
+        int processed = 0;
+        check(dmx_chunk_flags(m.chunk, &processed, nullptr, nullptr, nullptr));
+        if (!processed) {
+            // a map without a graph: no point has its node, the reference writes the header alone (no GPU needed)
+            perf.add("Load graph file", load_s + std::chrono::duration<double>(std::chrono::steady_clock::now() - t2).count());
+            timed(perf, "Writing pointmap connections", [&] { write_file(a.out, header); });
+            return;
+        }
+        const auto t3 = std::chrono::steady_clock::now();
+        Cp.reset(new Context());   // (the device context's creation does not count as loading, as in VGA)
+        Context& C = *Cp;
+        const auto t4 = std::chrono::steady_clock::now();
+        check(dmx_chunk_info(m.chunk, nullptr, nullptr, nullptr, nullptr, &m.nnodes, nullptr, nullptr, nullptr, nullptr));
+        check(dmx_chunk_load(C.ctx, m.chunk, d.region, &m.pm, &m.g));
+        perf.add("Load graph file",
+                 load_s + std::chrono::duration<double>((t3 - t2) + (std::chrono::steady_clock::now() - t4)).count());
+        timed(perf, "Writing pointmap connections", [&] {
+            std::ofstream f(a.out, std::ios::binary | std::ios::trunc);
+            f.write(header.data(), (std::streamsize)header.size());
+            const int64_t N = m.nnodes;
+            std::vector<int64_t> off((size_t)N + 1, 0);
+            int64_t size = 0;
+            check(dmx_graph_connections_csv(C.ctx, m.g, 0, -1, ",", off.data(), nullptr, 0, &size));
+            int64_t budget = dmx::policy::kConnTextBudget;
+            if (const char* e = dmx::policy::hook("DMX_CONN_BUDGET"))
+                if (std::atoll(e) > 0) budget = std::atoll(e);
+            std::vector<char> buf;
+            for (int64_t b = 0; b < N;) {
+                int64_t e = b + 1;   // at least one node, then as many as the budget holds
+                while (e < N && off[e + 1] - off[b] <= budget) e++;
+                const int64_t need = off[e] - off[b];
+                if (need > 0) {
+                    buf.resize((size_t)need);
+                    int64_t got = 0;
+                    check(dmx_graph_connections_csv(C.ctx, m.g, b, e, ",", nullptr, buf.data(), need, &got));
+                    if (got != need) throw RuntimeException("connections export: a range's size changed between calls");
+                    f.write(buf.data(), (std::streamsize)need);
+                }
+                b = e;
+            }
+            f.flush();
+            if (!f) throw RuntimeException("Failed to write " + a.out);
+        });
+    }
+};
+
 void print_help() {
     std::cout << "Usage: dmxcli -m <mode> -f <filename> -o <output file> [-t <times.csv>] [-s] [-p] [mode options]\n"
                  "Modes (the accelerated depthmapXcli path):\n"
                  "  VISPREP   -pg <grid spacing> -pp <x,y> | -pf <points file> [-pr <max visibility>] [-pb] [-pm]\n"
                  "  VGA       -vm visibility [-vl] [-vg -vr <radius|n>] | -vm metric -vr <radius|n> | -vm angular\n"
                  "  STEPDEPTH -sdt metric|visual|angular -sdp <x,y> | -sdf <points file>\n"
+                 "  EXPORT    -em pointmap-data-csv | pointmap-connections-csv | pointmap-links-csv\n"
+                 "            (the displayed point map as CSV; -o names the CSV file)\n"
                  "Input: a depthmapX .graph (written back as .graph), or a CSV drawing (x1,y1,x2,y2) / a .dmxg\n"
                  "written by this tool (written as .dmxg)\n";
 }
@@ -884,6 +1068,7 @@ int main(int argc, char* argv[]) {
     modes.emplace_back(new VisPrep());
     modes.emplace_back(new Vga());
     modes.emplace_back(new StepDepth());
+    modes.emplace_back(new Export());
     try {
         // CommandLineParser::parse (commandlineparser.cpp:51-133)
         if (argc <= 1) throw CommandLineException("No commandline parameters provided - don't know what to do");

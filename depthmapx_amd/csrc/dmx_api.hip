@@ -41,6 +41,7 @@
 #include "kernels/isovist.hip"
 #include "kernels/isovist_points.hip"
 #include "kernels/chunk_codec.hip"
+#include "kernels/connections.hip"
 
 using namespace dmx;
 
@@ -219,6 +220,9 @@ struct dmx_ctx {
     double sqrt_err = 0.0;            // makeGraph moment square root: measured error bound (mk_sqrt_err)
     long long sqrt_err_nmax = 0;      // ... over 1..sqrt_err_nmax
     long long last_fill_levels = 0;
+    double last_conn_s[2] = {0, 0};          // connections: counting pass and scan, emitting pass (kernels)
+    long long last_conn[4] = {0, 0, 0, 0};   // connections: bitmap in HBM, nodes with duplicates, cells dropped as
+                                             // duplicates, cells dropped outside the grid
 };
 
 struct dmx_pointmap {
@@ -729,6 +733,7 @@ int dmx_ctx_last_timing(dmx_ctx* c, double* mk, double* vga) {
 #include "api/vga_global.hip"
 #include "api/vga_other.hip"
 #include "api/thruvision.hip"
+#include "api/connections.hip"
 #include "api/isovist.hip"
 #include "api/isovist_points.hip"
 #include "api/stepdepth.hip"

@@ -99,6 +99,16 @@ constexpr int kIsoPointsMorton = 1;
 // keeps the pinned allocation short next to the copy it serves.  Hook: DMX_CODEC_SLAB (bytes; tests shrink it).
 constexpr int64_t kCodecSlabBytes = 64ll << 20;
 
+// ---- connections export (connections.hip, api/connections.hip, dmxcli -m EXPORT)
+// LDS the two kernels hold beside the per-node bitmap (run tile, prefix, text staging: 15.3 KiB in the emitting
+// kernel): the bitmap goes to per-workgroup HBM slices when bitmap + this exceeds kLdsPassBudget (grids above
+// ~1040^2 cells).  Hook: DMX_CONN_GBM (any value) forces the slices (tests).
+constexpr int kConnStaticLds = 16 * 1024;
+// bytes of CSV text dmxcli asks for in one dmx_graph_connections_csv call (a device buffer and a host copy of that
+// size, whatever the size of the export).  Hook: DMX_CONN_BUDGET (bytes; tests shrink it to a few KB, so that a small
+// map takes many ranges).  A node whose lines exceed the budget goes alone.
+constexpr int64_t kConnTextBudget = 256ll << 20;
+
 // ---- memory: optional summaries are built only within a share of the free device memory, so a graph
 // that fills the GPU still runs (on the slower exact path that needs no summary)
 // tile rows (tvis / ftvis) and partial-tile masks on narrow grids: a quarter of the free memory

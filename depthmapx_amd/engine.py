@@ -157,6 +157,16 @@ class Context:
         return dict(bsp_seconds=b.value, kernel_seconds=k.value, tree_nodes=int(d[0]), tree_depth=int(d[1]),
                     reruns=int(d[2]), max_blocks=int(d[3]))
 
+    def last_connections(self):
+        """The last Graph.connections / connections_csv (dmx_ctx_last_connections): kernel seconds of the counting
+        pass (with its scan) and of the emitting pass, whether the per-node bitmap lay in HBM slices, the nodes that
+        held a duplicate, and the cells dropped as duplicates and as lying outside the grid."""
+        c, e = ctypes.c_double(), ctypes.c_double()
+        d = np.zeros(4, dtype=np.int64)
+        N.check(N.lib().dmx_ctx_last_connections(self.h, ctypes.byref(c), ctypes.byref(e), N.ptr(d)))
+        return dict(count_seconds=c.value, emit_seconds=e.value, bitmap_hbm=int(d[0]), dup_nodes=int(d[1]),
+                    dup_cells=int(d[2]), outside_cells=int(d[3]))
+
     ISOVIST_POLY_GUESS = 128   # vertices a point the first call with polygons=True makes room for
 
     def isovists(self, lines, points, angles=None, region=None, simple=False, polygons=False):
@@ -492,6 +502,43 @@ class Graph:
         N.check(N.lib().dmx_vga_thruvision(self.ctx.h, self.h, int(src_begin), int(src_end), N.ptr(out),
                                            N.ptr(cnt)))
         return (out, cnt) if counts else out
+
+    def _node_range(self, node_begin, node_end):
+        nb, ne = int(node_begin), int(node_end)
+        return nb, ne, max((self.info()["nnodes"] if ne < 0 else ne) - nb, 0)
+
+    def connections(self, node_begin=0, node_end=-1, export=False):
+        """The neighbourhoods of the nodes [node_begin, node_end) expanded on the GPU (dmx_graph_connections): (off
+        int64 [n + 1], refs int32 [total]), the cells of node i at refs[off[i]:off[i + 1]] as packed PixelRefs
+        ((x << 16) + (y & 0xffff)) in the order and with the deduplication of Node::contents (ngraph.cpp:184-191).
+        export=True keeps only what PointMap::outputConnectionsAsCSV writes: filled cells behind the source in
+        x-major order.  One counting call, then one call with room for the result."""
+        nb, ne, n = self._node_range(node_begin, node_end)
+        off = np.zeros(n + 1, dtype=np.int64)
+        total = ctypes.c_int64()
+        lib = N.lib()
+        N.check(lib.dmx_graph_connections(self.ctx.h, self.h, nb, ne, int(bool(export)), N.ptr(off), None, 0,
+                                          ctypes.byref(total)))
+        refs = np.zeros(total.value, dtype=np.int32)
+        if total.value:
+            N.check(lib.dmx_graph_connections(self.ctx.h, self.h, nb, ne, int(bool(export)), N.ptr(off), N.ptr(refs),
+                                              len(refs), ctypes.byref(total)))
+        return off, refs
+
+    def connections_csv(self, node_begin=0, node_end=-1, delim=","):
+        """The edge lines of depthmapXcli -m EXPORT -em pointmap-connections-csv for the nodes of the range, as
+        bytes formatted on the GPU (dmx_graph_connections_csv): "\\n" + from + delim + to per edge, without the
+        header ("RefFrom" + delim + "RefTo").  The texts of consecutive ranges concatenate to their union's."""
+        nb, ne, _ = self._node_range(node_begin, node_end)
+        size = ctypes.c_int64()
+        lib = N.lib()
+        d = delim.encode() if isinstance(delim, str) else bytes(delim)
+        N.check(lib.dmx_graph_connections_csv(self.ctx.h, self.h, nb, ne, d, None, None, 0, ctypes.byref(size)))
+        buf = ctypes.create_string_buffer(max(size.value, 1))
+        if size.value:
+            N.check(lib.dmx_graph_connections_csv(self.ctx.h, self.h, nb, ne, d, None, buf, size.value,
+                                                  ctypes.byref(size)))
+        return buf.raw[:size.value]
 
     ISOVIST_COLUMNS = ["Isovist Area", "Isovist Compactness", "Isovist Drift Angle", "Isovist Drift Magnitude",
                        "Isovist Max Radial", "Isovist Min Radial", "Isovist Occlusivity", "Isovist Perimeter"]

@@ -67,7 +67,7 @@ typedef int32_t (*dmx_progress_fn)(void* user, int32_t phase, int64_t done, int6
 int dmx_ctx_set_progress(dmx_ctx* ctx, dmx_progress_fn fn, void* user, double interval_s);
 /* Request cancellation of the operation running on ctx (callable from any thread).  The request is
  * consumed by the operation that observes it; one made while no operation runs cancels the next
- * makegraph, VGA-global, through-vision, isovist or step-depth (metric, angular, visual) call at its first poll -- before that
+ * makegraph, VGA-global, through-vision, isovist, connections or step-depth (metric, angular, visual) call at its first poll -- before that
  * call writes any output.  VGA local / metric / angular do not poll (a pending request waits). */
 int dmx_ctx_cancel(dmx_ctx* ctx);
 /* Wall time of the kernels of the last makegraph / vga call, measured with HIP events on the
@@ -260,6 +260,40 @@ int dmx_vga_local(dmx_ctx* ctx, dmx_graph* g, int gates_only, int64_t src_begin,
  * cancel as in dmx_vga_global. */
 int dmx_vga_thruvision(dmx_ctx* ctx, dmx_graph* g, int64_t src_begin, int64_t src_end,
                        float* out /* host [N] */, int64_t* counts /* host [N], optional */);
+/* ---- Connections of the visibility graph (GPU) ------------------------------------------------- */
+/* Node::contents (salalib/ngraph.cpp:158-191, over Bin::first / next / cursor, :392-416) for the nodes
+ * [node_begin, node_end) (node_end < 0: all): the cells of each node's runs in the reference's order -- bins 0..31,
+ * the runs of a bin as stored, the cells of a run from its start along the bin's direction (a run's start is always
+ * visited; a diagonal bin is one span) -- without the cells that occurred earlier in the same node's enumeration
+ * (depthmapX::addIfNotExists keeps the first occurrence; a graph fresh from makeGraph has none, one read back from a
+ * .graph can, ngraph.cpp:536-563).  With DMX_CONN_EXPORT the list is cut down to what
+ * PointMap::outputConnectionsAsCSV (salalib/pointdata.cpp:656-681) writes for the node: the cells that are filled()
+ * and are not a node at or before the source in x-major order (here: FILLED, and cell > the source's cell).
+ * Divergence: a run shifted out of the grid by the format's 4-bit row shift makes the reference read points outside
+ * its matrix (undefined behaviour); here cells outside the grid are dropped.
+ *   off    host [n + 1] (n = nodes of the range), or NULL: the start of each node's cells in refs; off[n] = *total
+ *   refs   host [cap], or NULL: PixelRefs packed as the reference packs them, (x << 16) + (y & 0xffff)
+ * The capacity protocol is dmx_isovists': refs NULL or cap < *total sets off and *total only (DMX_OK); nothing is
+ * half written.  An empty range: DMX_OK.  Nodes the graph does not hold (a shard): DMX_ERR_STATE.  Progress and cancel
+ * as in dmx_vga_thruvision (phase DMX_PHASE_VGA, the unit is a node); on a cancel or an error no output is touched.
+ * The order of the output does not depend on scheduling (count, scan, emit: kernels/connections.hip). */
+#define DMX_CONN_EXPORT 1   /* apply outputConnectionsAsCSV's filter; 0: Node::contents */
+int dmx_graph_connections(dmx_ctx* ctx, dmx_graph* g, int64_t node_begin, int64_t node_end, int flags,
+                          int64_t* off /* [n+1] */, int32_t* refs /* [cap] or NULL */, int64_t cap, int64_t* total);
+/* The edge lines of PointMap::outputConnectionsAsCSV(stream, delim) (pointdata.cpp:656-681; depthmapXcli -m EXPORT
+ * -em pointmap-connections-csv, runmethods.cpp:662-669) for the nodes of the range, formatted on the device: per
+ * edge "\n" + from + delim + to, both PixelRefs as the decimal of the packed int (PixelRef::operator int).  The
+ * header "RefFrom" + delim + "RefTo" is the caller's; the texts of consecutive ranges, concatenated, are the text
+ * of their union.  off (optional) [n + 1]: the byte at which each node's lines start; buf NULL or cap < *size: only
+ * off and *size are set.  delim empty or longer than 8 bytes: DMX_ERR_ARG.  Otherwise as dmx_graph_connections. */
+int dmx_graph_connections_csv(dmx_ctx* ctx, dmx_graph* g, int64_t node_begin, int64_t node_end, const char* delim,
+                              int64_t* off /* [n+1] bytes, or NULL */, char* buf /* [cap] or NULL */, int64_t cap,
+                              int64_t* size);
+/* The last dmx_graph_connections / _csv call: kernel seconds of the counting pass with its scan and of the emitting
+ * pass (0 when nothing was emitted), and out4 = {1 when the per-node bitmap lay in per-workgroup HBM slices (grids
+ * whose bitmap does not fit LDS; 0: in LDS), nodes that held a duplicate, cells dropped as duplicates, cells dropped
+ * outside the grid}.  Any pointer may be NULL. */
+int dmx_ctx_last_connections(dmx_ctx* ctx, double* count_s, double* emit_s, int64_t* out4);
 /* ---- VGA isovist analysis (GPU) -------------------------------------------------------------- */
 /* MetaGraph::analyseGraph(OUTPUT_ISOVIST) -> VGAIsovist().run (salalib/mgraph.cpp:346-348,
  * vgamodules/vgaisovist.cpp:24-129; what depthmapXcli -m VGA runs without -vm): a BSP tree of the drawing lines
@@ -441,6 +475,15 @@ int dmx_pointmap_set_merges(dmx_pointmap* pm, const int32_t* cell_pairs, int64_t
 /* The merge links stored in a chunk, one entry per link (cell < partner cell): *n in = capacity of
  * cell_pairs ([n][2]), out = number of links; cell_pairs NULL: only *n. */
 int dmx_chunk_merges(const dmx_chunk* c, int32_t* cell_pairs, int64_t* n);
+/* The attribute rows of a chunk in table (key) order, for PointMap::outputSummary (pointdata.cpp:554-587): keys
+ * [nrows] the rows' PixelRefs as ints, visible [nrows] what isObjectVisible(m_layers, row) gives (layermanager.h:
+ * 84-87: the map's visible layers & the row's layer key).  nrows from dmx_chunk_flags; either may be NULL. */
+int dmx_chunk_rows(const dmx_chunk* c, int32_t* keys, uint8_t* visible);
+/* Point::m_merge as the chunk stores it, for PointMap::outputLinksAsCSV (pointdata.cpp:683-706): (cell, partner
+ * cell) of EVERY point with a link, in x-major order of the cell -- a link appears once per point that stores it,
+ * and nothing is checked (dmx_chunk_merges normalises and checks).  *n in = capacity of cell_pairs ([n][2]), out =
+ * the number of records; cell_pairs NULL: only *n. */
+int dmx_chunk_merge_records(const dmx_chunk* c, int32_t* cell_pairs, int64_t* n);
 /* Editing a parsed chunk the way the reference edits a PointMap it read (PointMap::read then ::write,
  * pointdata.cpp:1073-1188): columns that are not set keep their bytes (stats, display parameters,
  * formula), point records are re-emitted with the state bits PointMap::read keeps.
