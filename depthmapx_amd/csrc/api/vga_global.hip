@@ -664,6 +664,7 @@ static int launch_tile(dmx_ctx* ctx, const VgaTileParams& Q, int64_t nsrc, size_
     P.chunk = std::max(1, policy::hook_int("DMX_VGA_CHUNK", policy::kVgaSourceChunk));
     P.nwork = (int)((P.src_end - P.src_begin + P.chunk - 1) / P.chunk);
     P.bsplit = policy::hook_int("DMX_VGA_BSPLIT", policy::kVgaTileBSplit) & 3;
+    P.csplit = policy::hook_int("DMX_VGA_CSPLIT", policy::kVgaTileCSplit) & 1;
     P.walk = policy::hook_int("DMX_VGA_WALK", policy::kVgaTileWalk) != 0;
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     P.ctl = ctx->d_ctl;
@@ -831,9 +832,11 @@ static int vga_tile_impl(dmx_ctx* ctx, dmx_graph* g, double radius, int gates_on
     ctx->last_stats[30] = (long long)st[28];                          // phase-B cell-test clocks (not collected: 0)
     ctx->last_stats[31] = (long long)st[29];                          // phase-B cells past hint + 4 heads
     ctx->last_stats[23] = (long long)st[21];                          // phase-C busy clocks summed over waves
-    ctx->last_stats[24] = (long long)st[22];                          // phase-C per-cell clocks (not collected: 0)
+    // (slot 22 counts the row stage's cells; the attribution builds VGA_ROWSTAT / VGA_CSTAT put a diagnostic count there)
+    ctx->last_stats[24] = (VGA_ROWSTAT || VGA_CSTAT) ? (long long)st[22] : 0;   // phase-C per-cell clocks (not collected: 0)
     ctx->last_stats[25] = 0;                                          // phase-C special-node clocks (not collected: 0)
     ctx->last_stats[48] = (long long)st[23];                          // the longest tile list a walk took
+    ctx->last_stats[49] = (VGA_ROWSTAT || VGA_CSTAT) ? 0 : (long long)st[22];   // phase-C cells through the row stage
     ctx->last_stats[26] = (long long)st[24];                          // phase-C special-node tests
     ctx->last_stats[3] = 3 | ((long long)g->nspecial << 8);
     ctx->last_stats[4] = (long long)st[0];
@@ -993,6 +996,7 @@ static int vga_impl(dmx_ctx* ctx, dmx_graph* g, double radius, int gates_only, i
     ctx->last_stats[40] = 0;   // (the tile search sets its preparation flags; the other searches leave none)
     ctx->last_stats[43] = 0;
     ctx->last_stats[48] = 0;   // (the tile search's longest tile list)
+    ctx->last_stats[49] = 0;   // (its hard cells through the row stage)
     PointMapHost& h = *g->pm->host;
     const int tw = (h.cols() + 7) / 8, th = (h.rows() + 7) / 8;
     const int maxlev = 4096;

@@ -15,8 +15,10 @@
 //       B. a wave per remaining tile, lane = cell: the tile-to-tile rows (ttvis / ttany), then each cell's
 //          first head runs and its hint (the run or partial-tile mask that last hit), then the other heads;
 //       C. hard cells, a wave per cell: the tile-visibility rows (tvis / ftvis) give a certain hit or miss,
-//          the partial-tile masks decide the rest exactly; without the masks (memory, grids above 1024 a
-//          side) the cell's runs are scanned, with the tvis rows (and their summaries) as a miss certificate;
+//          the partial-tile masks decide the rest exactly (the regular cells of a chunk in a loop of their own,
+//          c1_chunk: rows as unpredicated range-checked buffer loads, hints written once a chunk); without the
+//          masks (memory, grids above 1024 a side) the cell's runs are scanned, with the tvis rows (and their
+//          summaries) as a miss certificate;
 //   * top-down again when Beamer's test prefers it (small frontier); the bookkeeping publishes the
 //     expandable part of X as the next F and rebuilds F's summaries.
 // DESIGN.md section 2 has the measurements behind each choice, including the variants measured and dropped
@@ -100,6 +102,7 @@ struct VgaTileParams {
     int bext;                 // phase-B runs after the heads (BEXT_DEFAULT)
     int crk;                  // tile-common runs tested in phase A (<= CRK)
     int bsplit;               // phase B in stages: bit 0 row stage + cell stage, bit 1 extension stage (0: fused)
+    int csplit;               // phase C in stages: bit 0 row stage (a chunk's regular cells in a loop of their own, c1_chunk; 0: in the chunk's one loop)
     int walk;                 // the tile walks take VGA_WALK_NF tiles a thread at once, level 1 is built in place (0: a tile at a time)
     const int2* mpairs;      // [nmp] merge links (cell a, cell b), x-major (Point::m_merge; nullptr: none)
     int nmp;
@@ -215,6 +218,10 @@ struct FView {
 #endif
 #ifndef VGA_PHASEC_ROWSONLY
 #define VGA_PHASEC_ROWSONLY 0
+#endif
+#ifndef VGA_CSTAT
+#define VGA_CSTAT 0          // diagnostic build: phase C's undecided cells counted by word items, masks and mask rounds
+                             // (in the slots of vga_c_scan, vga_b_row_cycles, vga_b_cell_cycles, vga_hard_runs: profiles/vga_cstages_ab.txt)
 #endif
 #ifndef VGA_HINTS
 #define VGA_HINTS 4          // hint slots a cell (narrow grids with the masks): the hint + VGA_HINTS - 1 fully seen
@@ -597,34 +604,62 @@ __device__ __forceinline__ void hint2_push(const VgaTileParams& P, int id, uint3
     P.hint2[id] = hold;
 }
 
-// C_FUSED: the row test and the mask test in one pass per cell (no separate row-test pass over the chunk):
-// the 4 row words of tvis and ftvis a lane owns are loaded together, a frontier tile under the full row is a
-// certain hit, none under the partial bits a certain miss, else the masks of the partial frontier tiles.
-__device__ __forceinline__ bool pmask_hit_fused(const VgaTileParams& P, const unsigned long long* F,
-                                                const unsigned long long* Fsr, int id, unsigned& nload, uint32_t* Hn,
-                                                int& how, unsigned nzb = 0xFu, unsigned* rstat = nullptr) {
-    const int lane = threadIdx.x & 63;
+// A hard cell's loads for the exact test below: the 4 + 4 row words of tvis and ftvis a lane owns under the frontier
+// tile rows, 16 registers a lane.
+struct CRow {
+    unsigned long long t[4], f[4];
+};
+// A wave-uniform pointer as scalar registers (two readfirstlanes), for a buffer descriptor.
+__device__ __forceinline__ const void* uni_ptr(const void* p) {
+    return (const void*)(uintptr_t)uni64((unsigned long long)(uintptr_t)p);
+}
+__device__ __forceinline__ unsigned long long buf_load64(__amdgpu_buffer_rsrc_t rs, int off) {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0);
+    return (unsigned long long)v[0] | ((unsigned long long)v[1] << 32);
+}
+// Issue the loads of cell `id`.  nzb: the lane's row words that are non-zero (tvnz; ftvis lies in tvis).  The row
+// words are buffer loads through a descriptor of the cell's row (tvw words): a lane with nothing to read (no frontier
+// tile under its word, a word past the row) gives the offset of the row's end, which the range check answers with zero
+// without touching memory.  So the loads are not predicated: the 8 of a cell leave back to back from one basic block
+// (predicated a lane they were four branches a cell, each pair of loads behind its own exec mask).
+__device__ __forceinline__ void crow_load(const VgaTileParams& P, const unsigned long long* Fsr, int id, unsigned nzb,
+                                          CRow& r) {
+    const int lane = lanes_below(~0ull);
+    const int tvw = P.tvw;
+    const size_t row = (size_t)id * tvw;
+    const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc((void*)uni_ptr(P.tvis + row), 0, tvw * 8, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc((void*)uni_ptr(P.ftvis + row), 0, tvw * 8, 0x00020000);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int w = k * 64 + lane;
+        const unsigned long long fs = Fsr[min(w, tvw - 1)];
+        const int off = (w < tvw && fs != 0ull && ((nzb >> k) & 1u)) ? w * 8 : tvw * 8;
+        r.t[k] = buf_load64(rt, off);
+        r.f[k] = buf_load64(rf, off);
+    }
+}
+
+// The exact test of a hard cell from its loaded rows: a frontier tile under the full row is a certain hit, none
+// under the partial bits a certain miss, else the masks of the partial frontier tiles.  (F and Fsr do not change
+// within a level.)  It stores nothing: a hit returns the cell's new hint in hnew (uniform; cell_hint_write stores it),
+// so that the row stage's loop over a chunk holds no store.
+__device__ __forceinline__ bool pmask_hit_rows(const VgaTileParams& P, const unsigned long long* F,
+                                               const unsigned long long* Fsr, int id, unsigned& nload, uint32_t& hnew,
+                                               int& how, const CRow& r, unsigned nzb = 0xFu, unsigned* rstat = nullptr) {
+    const int lane = lanes_below(~0ull);
     const int tvw = P.tvw, tw = P.tw, wr = (P.tw + 63) / 64;
     const size_t row = (size_t)id * tvw;
     unsigned long long pw[4], cw[4];
     int base[4];
     bool cert = false;
     int ct = -1;   // a frontier tile the cell sees completely (the lane's first): k << 6 | bit
-    // the hint a hit here replaces: a fully seen tile moves to the second hint (loaded with the rows)
-    const uint32_t hold = P.hint2 ? Hn[id] : 0xFFFFFFFFu;
-    uint32_t h2old[VGA_H2 > 1 ? VGA_H2 - 1 : 1];   // the slots that shift down when the hint moves into hint2
-#pragma unroll
-    for (int k = 0; k + 1 < VGA_H2; k++) h2old[k] = P.hint2 ? P.hint2[(size_t)k * P.tw * P.th * 64 + id] : 0xFFFFFFFFu;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const int w = k * 64 + lane;
-        const unsigned long long fs = w < tvw ? Fsr[w] : 0ull;
-        unsigned long long t = 0ull, f = 0ull;
+        const unsigned long long fsw = Fsr[min(w, tvw - 1)];
+        const unsigned long long fs = w < tvw ? fsw : 0ull;
+        const unsigned long long t = r.t[k], f = r.f[k];
         base[k] = 0;
-        if (fs && ((nzb >> k) & 1u)) {   // nzb: the lane's row words that are non-zero (tvnz; ftvis lies in tvis)
-            t = P.tvis[row + w];
-            f = P.ftvis[row + w];
-        }
         if (ct < 0 && (f & fs) != 0ull) ct = (k << 6) | (__ffsll((long long)(f & fs)) - 1);
         cert |= (f & fs) != 0ull;
         pw[k] = t & ~f;
@@ -637,17 +672,13 @@ __device__ __forceinline__ bool pmask_hit_fused(const VgaTileParams& P, const un
         }
 #endif
     }
+    // the hint a hit here replaces: a fully seen tile moves to the second hint (loaded with the rows)
     if (const unsigned long long cb = __ballot(cert)) {
         // the next source's phase B tests that tile first (slot 0xFFFF: the whole tile, no mask)
-        if (lane == __ffsll((long long)cb) - 1) {
-            const int w = (ct >> 6) * 64 + lane;
-            const int t = (w / wr) * tw + (w % wr) * 64 + (ct & 63);
-            const uint32_t hnew = 0x80000000u | ((uint32_t)t << 16) | 0xFFFFu;
-            if (P.hint2 && (hold & 0x8000FFFFu) == 0x8000FFFFu && hold != 0xFFFFFFFFu && hold != hnew) {
-                hint2_push(P, id, hold, h2old);
-            }
-            Hn[id] = hnew;
-        }
+        const int fl = __ffsll((long long)cb) - 1, ctl = __builtin_amdgcn_readlane(ct, fl);
+        const int w = (ctl >> 6) * 64 + fl;
+        const int t = (w / wr) * tw + (w % wr) * 64 + (ctl & 63);
+        hnew = 0x80000000u | ((uint32_t)t << 16) | 0xFFFFu;
         how = 1;
         return true;
     }
@@ -655,6 +686,15 @@ __device__ __forceinline__ bool pmask_hit_fused(const VgaTileParams& P, const un
     how = 0;
 #if VGA_PHASEC_ROWSONLY
     return false;   // attribution build: no mask loads (results differ)
+#endif
+#if VGA_CSTAT
+    if (rstat) {   // diagnostic build: the undecided cell's word items and the masks they could load
+        rstat[0] += __popcll(__ballot((cw[0] != 0ull))) + __popcll(__ballot((cw[1] != 0ull))) +
+                    __popcll(__ballot((cw[2] != 0ull))) + __popcll(__ballot((cw[3] != 0ull)));
+        unsigned pc = __popcll(cw[0]) + __popcll(cw[1]) + __popcll(cw[2]) + __popcll(cw[3]);
+        for (int off = 32; off >= 1; off >>= 1) pc += __shfl_xor(pc, off);
+        rstat[1] += pc;
+    }
 #endif
 #pragma unroll
     for (int k = 0; k < 4; k++) base[k] = cw[k] ? (int)P.ppre[row + k * 64 + lane] : 0;
@@ -670,6 +710,9 @@ __device__ __forceinline__ bool pmask_hit_fused(const VgaTileParams& P, const un
             constexpr int NM = 4;   // masks a lane keeps in flight (2: +1 %, 8: +34 %, round 4)
             unsigned long long mk[NM];
             int tl[NM], sl[NM];
+#if VGA_CSTAT
+            if (rstat) rstat[2]++;   // (a mask round: a dependent trip)
+#endif
 #pragma unroll
             for (int j = 0; j < NM; j++) {
                 tl[j] = -1;
@@ -688,17 +731,110 @@ __device__ __forceinline__ bool pmask_hit_fused(const VgaTileParams& P, const un
                 if (tl[j] >= 0 && (F[tl[j]] & mk[j])) { hj = j; ht = tl[j]; hq = sl[j]; }
             const unsigned long long hb = __ballot(hj >= 0);
             if (hb != 0ull) {
-                if (lane == __ffsll((long long)hb) - 1) {
-                    if (P.hint2 && (hold & 0x8000FFFFu) == 0x8000FFFFu && hold != 0xFFFFFFFFu) {
-                        hint2_push(P, id, hold, h2old);
-                    }
-                    Hn[id] = 0x80000000u | ((uint32_t)ht << 16) | (uint32_t)hq;
-                }
+                const int fl = __ffsll((long long)hb) - 1;
+                hnew = 0x80000000u | ((uint32_t)__builtin_amdgcn_readlane(ht, fl) << 16) | (uint32_t)__builtin_amdgcn_readlane(hq, fl);
                 return true;
             }
         }
     }
     return false;
+}
+
+// A hit of the exact test replaces the cell's hint `hold` by hnew (one lane calls): a fully seen tile the hint held
+// moves to the front of hint2 (h2old: its slots before the last).
+__device__ __forceinline__ void cell_hint_write(const VgaTileParams& P, uint32_t* Hn, int id, uint32_t hnew, uint32_t hold,
+                                                const uint32_t* h2old) {
+    if (P.hint2 && (hold & 0x8000FFFFu) == 0x8000FFFFu && hold != 0xFFFFFFFFu && hold != hnew) hint2_push(P, id, hold, h2old);
+    Hn[id] = hnew;
+}
+
+// C_FUSED: the row test and the mask test in one pass per cell (no separate row-test pass over the chunk): the
+// cell's loads go out together and are used at once (one cell in flight a wave).
+__device__ __forceinline__ bool pmask_hit_fused(const VgaTileParams& P, const unsigned long long* F,
+                                                const unsigned long long* Fsr, int id, unsigned& nload, uint32_t* Hn,
+                                                int& how, unsigned nzb = 0xFu, unsigned* rstat = nullptr) {
+    // the hint a hit here replaces: a fully seen tile moves to the second hint (loaded with the rows)
+    const uint32_t hold = P.hint2 ? Hn[id] : 0xFFFFFFFFu;
+    uint32_t h2old[VGA_H2 > 1 ? VGA_H2 - 1 : 1];   // the slots that shift down when the hint moves into hint2
+#pragma unroll
+    for (int k = 0; k + 1 < VGA_H2; k++) h2old[k] = P.hint2 ? P.hint2[(size_t)k * P.tw * P.th * 64 + id] : 0xFFFFFFFFu;
+    CRow r;
+    crow_load(P, Fsr, id, nzb, r);
+    uint32_t hnew = 0xFFFFFFFFu;
+    const bool found = pmask_hit_rows(P, F, Fsr, id, nload, hnew, how, r, nzb, rstat);
+    if (found && (threadIdx.x & 63) == 0) cell_hint_write(P, Hn, id, hnew, hold, h2old);
+    return found;
+}
+
+// Row words k*64 + lane (k < 4) that are non-zero for the cell of chunk entry j, from the chunk's tvnz words (nzp: lane
+// 4j + k holds summary word k of entry j); all four without the summaries.
+__device__ __forceinline__ unsigned chunk_nzb(unsigned long long nzp, int j, bool use_nz) {
+    unsigned nzb = 0xFu;
+    if (VGA_TVNZ && use_nz) {
+        const int lane = lanes_below(~0ull);
+        nzb = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const unsigned long long sk =
+                (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)nzp, j * 4 + k) |
+                ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(nzp >> 32), j * 4 + k) << 32);
+            nzb |= (unsigned)((sk >> lane) & 1ull) << k;
+        }
+    }
+    return nzb;
+}
+
+// Phase C's row stage over one chunk of the hard list: the entries of `stm` (bit j: entry j, held in lane j of myv;
+// regular cells) one after another: a cell's 8 row loads go out in one burst (crow_load) and the cell is reduced at once
+// to its decision (an undecided cell runs the mask loop from its own rows).  The loop holds no store: lane j keeps entry
+// j's new hint, and the chunk's hints are read and written at the end, a hit cell a lane.  F and Fsr are in LDS (the
+// stage runs on grids whose frontier fits it).  SC: the workgroup's counters (attribution builds only).
+struct C1Out {
+    unsigned long long found;   // bit j: entry j hit
+    unsigned nl;                // masks this lane loaded
+    int cert, prun;             // certain hits, certain misses
+};
+__device__ __forceinline__ C1Out c1_chunk(const VgaTileParams& P, const unsigned long long* F, const unsigned long long* Fsr,
+                                          uint32_t* Hn, unsigned long long* SC, int myv, unsigned long long stm,
+                                          unsigned long long nzp, bool use_nz) {
+    const int lane = lanes_below(~0ull);
+    C1Out o;
+    o.found = 0ull; o.nl = 0u; o.cert = 0; o.prun = 0;
+    uint32_t myh = 0xFFFFFFFFu;   // lane j: the new hint of entry j, if it hit
+    for (unsigned long long sm = stm; sm != 0ull; sm &= sm - 1ull) {
+        const int j = __ffsll((long long)sm) - 1;
+        const int id = __builtin_amdgcn_readlane(myv, j);
+        const unsigned nzb = chunk_nzb(nzp, j, use_nz);
+        int how = 0;
+#if VGA_ROWSTAT || VGA_CSTAT
+        unsigned rsv[3] = {0u, 0u, 0u};
+        unsigned* const rsp = rsv;
+#else
+        unsigned* const rsp = nullptr;
+#endif
+        CRow r;
+        crow_load(P, Fsr, id, nzb, r);
+        uint32_t hnew = 0xFFFFFFFFu;
+        const bool found = pmask_hit_rows(P, F, Fsr, id, o.nl, hnew, how, r, nzb, rsp);
+        if (lane == j) myh = hnew;
+#if VGA_ROWSTAT
+        if (lane == 0) { atomicAdd(&SC[22], (unsigned long long)rsv[0]); atomicAdd(&SC[26], (unsigned long long)rsv[1]); atomicAdd(&SC[28], (unsigned long long)rsv[2]); }
+#elif VGA_CSTAT
+        if (lane == 0 && rsv[0]) { atomicAdd(&SC[26], (unsigned long long)rsv[0]); atomicAdd(&SC[28], (unsigned long long)rsv[1]); atomicAdd(&SC[15], (unsigned long long)rsv[2]); }
+#endif
+        o.cert += how == 1;
+        o.prun += how == 2;
+        if (found) o.found |= 1ull << j;
+    }
+    // the chunk's hints, a hit cell a lane: the hint it replaces and hint2's slots are read here, once a chunk
+    if ((o.found >> lane) & 1ull) {
+        uint32_t hold = 0xFFFFFFFFu, h2old[VGA_H2 > 1 ? VGA_H2 - 1 : 1];
+        if (P.hint2) hold = Hn[myv];
+#pragma unroll
+        for (int k = 0; k + 1 < VGA_H2; k++) h2old[k] = P.hint2 ? P.hint2[(size_t)k * P.tw * P.th * 64 + myv] : 0xFFFFFFFFu;
+        cell_hint_write(P, Hn, myv, myh, hold, h2old);
+    }
+    return o;
 }
 
 // The exact test on wide grids (tvw > 256 row words, row summaries tvsum), as pmask_hit_fused: a frontier tile
@@ -1486,11 +1622,15 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                 sync_global();
                 if (tid == 0) { const unsigned long long n = __builtin_amdgcn_s_memtime(); ST(10, n - tmark); tmark = n; }
                 const int hn = uni(S.hn);
-                // ---- C: hard cells.  A wave grabs CCH list entries at once (one coalesced load);
-                // C0 tests their tile-visibility rows two cells at a time (16 row words a lane in
-                // flight): a frontier tile the cell sees completely is a certain hit (regular cell:
-                // in-set == out-set), no tile in view holding a frontier cell a certain miss.  C1
-                // scans the run lists of the undecided cells, CSTEP * 64 runs a step (CSTEP loads a lane).
+#if VGA_CSTAT
+                if (tid == 0) atomicMax(&SC[22], (unsigned long long)hn);   // the longest hard list of a level
+#endif
+                // ---- C: hard cells.  A wave grabs CCH list entries at once (one coalesced load).
+                // With the masks: the row stage (c1_chunk) takes the chunk's regular cells, the loop behind it
+                // the special ones.  Without them: a row pass tests the tile-visibility rows two cells at a
+                // time (16 row words a lane in flight): a frontier tile the cell sees completely is a certain
+                // hit (regular cell: in-set == out-set), no tile in view holding a frontier cell a certain miss;
+                // the run scan then takes the undecided cells, CSTEP * 64 runs a step (CSTEP loads a lane).
                 constexpr int CCH = VGA_CCH;
                 // runs a lane loads per scan step (1000^2: 4 -> 9.61 s, 8 -> 9.71 s, 16 -> 14.6 s: more loads
                 // in flight per round trip do not pay for the registers and the over-read past the first hit)
@@ -1504,7 +1644,7 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                     const int cn = min(CCH, hn - it0);
                     const int myv = lane < cn ? L[it0 + lane] : -1;
                     // the chunk's non-zero row summaries (tvnz), one load: lane 4j + k holds word k of entry j
-                    static_assert(CCH * 4 <= 64, "tvnz prefetch: 4 summary words an entry");
+                    static_assert(!VGA_TVNZ || CCH * 4 <= 64, "tvnz prefetch: 4 summary words an entry");
                     unsigned long long nzp = ~0ull;
                     if (VGA_TVNZ && !FG && P.tvnz) {
                         const int jj = lane >> 2, kk = lane & 3, tvsw = (P.tvw + 63) >> 6;
@@ -1589,24 +1729,31 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                     }
                     unsigned long long found_m = certain_m;
                     int cf_n = 0, cf_cert = 0, cf_prun = 0, cf_hit = 0;   // (uniform: the mask test's outcomes are ballots)
+                    int c1n = 0;   // cells through the row stage
+                    const bool use_nz = VGA_TVNZ && !FG && P.tvnz;
+                    // The row stage (P.csplit bit 0; DESIGN.md section 2 "phase C in stages"): the chunk's regular
+                    // entries on the fused path are walked first, in a loop of their own (c1_chunk).  Special
+                    // entries, the wide path and the run scan take the loop below.
+                    const bool c1 = !VGA_PHASEC_OFF && !FG && (P.csplit & 1) && P.pmask;
+                    const unsigned long long stm = c1 ? __ballot(lane < cn && myv >= 0) & ~(certain_m | pruned_m) : 0ull;
+                    if (stm) {
+                        const C1Out co = c1_chunk(P, F, Fsr, Hn, SC, myv, stm, nzp, use_nz);
+                        found_m |= co.found;
+                        nlt += co.nl;
+                        cf_n += __popcll(stm);
+                        cf_cert += co.cert;
+                        cf_prun += co.prun;
+                        cf_hit += __popcll(co.found);
+                        c1n = __popcll(stm);
+                    }
                     for (int j = 0; j < cn; j++) {
-                        if (((certain_m | pruned_m) >> j) & 1ull) continue;
+                        if (((certain_m | pruned_m | stm) >> j) & 1ull) continue;
                         int id = __builtin_amdgcn_readlane(myv, j);
                         const bool special = id < 0;
                         if (special) id = -1 - id;
                         bool found = false;
                         int nr = 0;
-                        unsigned nzb = 0xFu;   // row words k*64 + lane (k < 4) that are non-zero for the cell
-                        if (VGA_TVNZ && !FG && P.tvnz) {
-                            nzb = 0u;
-#pragma unroll
-                            for (int k = 0; k < 4; k++) {
-                                const unsigned long long sk =
-                                    (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)nzp, j * 4 + k) |
-                                    ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(nzp >> 32), j * 4 + k) << 32);
-                                nzb |= (unsigned)((sk >> lane) & 1ull) << k;
-                            }
-                        }
+                        const unsigned nzb = chunk_nzb(nzp, j, use_nz);
                         if (SPECIAL && special) {
                             int x, y;
                             xy_of_tile_id(id, tw, x, y);
@@ -1627,12 +1774,19 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                             int how = 0;
 #if VGA_PHASEC_OFF
                             found = false;   // attribution build: phase C reads nothing (results differ)
-#elif VGA_ROWSTAT
-                            unsigned rsv[3] = {0u, 0u, 0u};
-                            found = (FG && P.tvsum) ? pmask_hit_wide(P, F, Fsr, id, nl) : pmask_hit_fused(P, F, Fsr, id, nl, Hn, how, nzb, rsv);
-                            if (lane == 0) { ST(22, rsv[0]); ST(26, rsv[1]); ST(28, rsv[2]); }
 #else
-                            found = (FG && P.tvsum) ? pmask_hit_wide(P, F, Fsr, id, nl) : pmask_hit_fused(P, F, Fsr, id, nl, Hn, how, nzb);
+#if VGA_ROWSTAT || VGA_CSTAT
+                            unsigned rsv[3] = {0u, 0u, 0u};
+                            unsigned* const rsp = rsv;
+#else
+                            unsigned* const rsp = nullptr;
+#endif
+                            found = (FG && P.tvsum) ? pmask_hit_wide(P, F, Fsr, id, nl) : pmask_hit_fused(P, F, Fsr, id, nl, Hn, how, nzb, rsp);
+#if VGA_ROWSTAT
+                            if (lane == 0) { ST(22, rsv[0]); ST(26, rsv[1]); ST(28, rsv[2]); }
+#elif VGA_CSTAT
+                            if (lane == 0 && rsv[0]) { ST(26, rsv[0]); ST(28, rsv[1]); ST(15, rsv[2]); }
+#endif
 #endif
                             // counted per chunk and per source (a butterfly over nl and five counter adds a
                             // hard cell, 1.76e9 cells a launch at 1000^2: VGA 3.35 -> 3.15 s)
@@ -1691,6 +1845,9 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                         if (cf_cert) ST(16, cf_cert);
                         if (cf_prun) ST(13, cf_prun);
                         if (cf_hit) ST(1, cf_hit);
+#if !VGA_ROWSTAT && !VGA_CSTAT
+                        if (c1n) ST(22, c1n);
+#endif
                     }
                 }
                 if (lane == 0) ST(21, __builtin_amdgcn_s_memtime() - c_t0);
@@ -2034,7 +2191,7 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
     __syncthreads();
     for (int i = tid; i < 32; i += NT)
         if (SC[i]) {
-            if (i == 23) atomicMax(&P.stats[i], SC[i]);   // the longest tile list: a maximum, not a sum
+            if (i == 23 || (VGA_CSTAT && i == 22)) atomicMax(&P.stats[i], SC[i]);   // the longest tile list: a maximum, not a sum
             else atomicAdd(&P.stats[i], SC[i]);
         }
 #undef ST

@@ -36,6 +36,14 @@ constexpr int kVgaSourceChunk = 1;
 // lists the cells that miss their first heads and hints and tests their other runs a cell a lane.  0 is the fused
 // loop (a wave a tile through rows, cells and extension).  Hook: DMX_VGA_BSPLIT (0..3; A/B records, tests).
 constexpr int kVgaTileBSplit = 3;
+// phase C of a bottom-up level in stages ("phase C in stages"): bit 0 walks the regular cells of a
+// hard-list chunk in a loop of their own (c1_chunk): no store in the loop, the chunk's hints written once at its end.
+// 0 keeps every cell in the chunk's one loop with the special entries and writes each hint at its hit.  Both read a
+// cell's rows with the same buffer loads (crow_load) and test them with the same code (pmask_hit_rows), so the switch
+// checks the loop and the hint writes, not the row read; the other searches and the tests' restatement check that.
+// (Bit 1 is kept for a mask stage, which is not built: the hook masks it off.)  Like DMX_VGA_BSPLIT a correctness
+// switch for tests and bisecting: timings are taken against the parent build.  Hook: DMX_VGA_CSPLIT (0 / 1).
+constexpr int kVgaTileCSplit = 1;
 // the tile walks of a level (phase A, the level bookkeeping, X = F & ~V) take VGA_WALK_NF tiles a thread at once, all
 // their loads in flight before the first is used, and a plain source builds its level 1 in place (DESIGN.md section 2,
 // "tile walks").  0 selects the loops that take a tile at a time.  A correctness switch for tests and bisecting, not
