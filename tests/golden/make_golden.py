@@ -33,7 +33,32 @@ CASES = {
     "syn128sd": ("inputs/syn128.csv", 1.0, ["0.5,0.5"], False, False, False),   # step depths only
     # inexact world coordinates (gen_synthetic.py NOISY_ROOMS: `gen_synthetic.py room os07 inputs/os07.csv`)
     "os07": ("inputs/os07.csv", 0.7, ["530644.24,183508.64"], True, True, True),
+    # makeGraph options (a 7th item: maxdist and / or boundary, the probe's --maxdist / --boundary; "base": the case
+    # whose drawing lines these share).  5.0 and 1.0 (25 cells of 0.04) are tie radii: thousands of cell pairs lie
+    # exactly at them (3-4-5, 7-24-25) or within an ulp or two (the inexact 0.04 coordinates).  The boundary graphs
+    # keep 315 of syn32's 961 nodes and 1772 of gallery's 4332.
+    "syn32_md5": ("inputs/syn32.csv", 1.0, ["0.5,0.5"], True, True, True, dict(base="syn32", maxdist=5.0)),
+    "syn32_b": ("inputs/syn32.csv", 1.0, ["0.5,0.5"], True, True, True, dict(base="syn32", boundary=True)),
+    "syn32_b_md5": ("inputs/syn32.csv", 1.0, ["0.5,0.5"], True, True, True,
+                    dict(base="syn32", maxdist=5.0, boundary=True)),
+    "gallery_md1": (REF + "/testdata/gallery_empty.graph", 0.04, ["1.32,7.24"], True, True, False,
+                    dict(base="gallery", maxdist=1.0)),
+    "gallery_b": (REF + "/testdata/gallery_empty.graph", 0.04, ["1.32,7.24"], True, True, False,
+                  dict(base="gallery", boundary=True)),
 }
+OPTION_CASES = [k for k, v in CASES.items() if len(v) > 6]
+
+
+def case_options(name):
+    """(maxdist, boundary, base case or None) of a case; -1.0 / False / None for the 6-item tuples."""
+    opt = CASES[name][6] if len(CASES[name]) > 6 else {}
+    return float(opt.get("maxdist", -1.0)), bool(opt.get("boundary", False)), opt.get("base")
+
+
+def probe_option_args(name):
+    maxdist, boundary, _ = case_options(name)
+    return (["--maxdist", repr(maxdist)] if maxdist != -1.0 else []) + (["--boundary"] if boundary else [])
+
 
 # step depth selections per case (STEPDEPTH -sdt metric|visual -sdp x,y [-sdp ...]); the probe runs
 # both step types on the same selection
@@ -45,6 +70,13 @@ STEPDEPTH = {
     "gallery": ["1.32,7.24"],
     "barnsbury": ["531000,184000"],
     "syn128sd": ["64.5,64.5", "3.5,120.5"],
+    # cells that are still nodes of the boundary graphs (syn32 cell (13, 16), gallery cell (58, 38)): run_case
+    # asserts it on the reference's own states
+    "syn32_md5": ["13.0,16.0"],
+    "syn32_b": ["13.0,16.0"],
+    "syn32_b_md5": ["13.0,16.0"],
+    "gallery_md1": ["2.96,6.32"],
+    "gallery_b": ["2.96,6.32"],
 }
 
 
@@ -72,13 +104,15 @@ def parse_grid(path):
 
 
 def run_case(name):
-    src, spacing, fills, vga, rt, keep = CASES[name]
+    src, spacing, fills, vga, rt, keep = CASES[name][:6]
+    maxdist, boundary, base = case_options(name)
     src_path = src if os.path.isabs(src) else os.path.join(HERE, src)
     with tempfile.TemporaryDirectory() as d:
         cmd = [PROBE, "--graph" if src_path.endswith(".graph") else "--lines", src_path,
                "--spacing", str(spacing), "--out", d]
         for p in fills:
             cmd += ["--fill", p]
+        cmd += probe_option_args(name)
         if vga:
             cmd += ["--vga"]
         if rt:
@@ -118,13 +152,21 @@ def run_case(name):
             arrays["stepdepth"] = rd("stepdepth.bin", np.float32).reshape(N, 3)
             arrays["stepdepth_sel"] = rd("stepdepth_sel.bin", np.int32)
             arrays["vstepdepth"] = rd("vstepdepth.bin", np.float32)
-    lines_npy = name + "_lines.npy"
-    np.save(os.path.join(HERE, lines_npy), lines)
+            sel = arrays["stepdepth_sel"]
+            # every selected cell is a node of the made graph (the boundary option unfills most cells)
+            assert len(sel) and (state[(sel >> 16) * int(g["rows"]) + (sel & 0xFFFF)] & 2).all(), (name, sel)
+        assert int(((state & 2) != 0).sum()) == N == int(g["filled"])
+    if base:   # the base case's drawing, not stored again
+        lines_npy = base + "_lines.npy"
+        assert np.array_equal(np.load(os.path.join(HERE, lines_npy)), lines)
+    else:
+        lines_npy = name + "_lines.npy"
+        np.save(os.path.join(HERE, lines_npy), lines)
     np.savez_compressed(os.path.join(HERE, name + ".npz"), **arrays)
     meta = dict(source=os.path.basename(src), spacing=spacing, fills=[[float(v) for v in p.split(",")] for p in fills],
                 region=g["region"], cols=int(g["cols"]), rows=int(g["rows"]), bottom_left=g["bottom_left"],
                 nodes=N, runs=int(g["runs"]), lines_npy=lines_npy, vga=vga, roundtrip=rt, full_runs=keep,
-                stepdepth=STEPDEPTH.get(name, []),
+                stepdepth=STEPDEPTH.get(name, []), maxdist=maxdist, boundary=boundary,
                 ref_seconds=dict(makegraph=g["t_makegraph"], vga=g["t_vga"], stepdepth=g.get("t_stepdepth", 0.0),
                                  vstepdepth=g.get("t_vstepdepth", 0.0)))
     return meta

@@ -60,6 +60,8 @@ REF_INPUTS = [
     ("mixed_link", "@mixed_made", ["-m", "LINK"] + sum([["-lnk", _cell_pt(*a) + "," + _cell_pt(*b)] for a, b in LINKS], [])),
 ]
 
+BOUNDARY_SDP = "2.96,6.32"   # gallery cell (58, 38): main() asserts that the reference's boundary graph kept it
+
 INPUTS = ["gallery_empty.graph", "gallery_connected.graph", "turns_connected.graph", "rect1x1.graph",
           "barnsbury_drawing.graph", "polygons_drawing.graph"]
 
@@ -84,6 +86,10 @@ CASES = [
      True, "(-pb boundary graph)"),
     ("gallery_maxdist", "gallery_empty.graph", ["-m", "VISPREP", "-pg", "0.04", "-pp", "1.32,7.24", "-pm", "-pr", "1.5"],
      [], True, "(-pr restricted visibility)"),
+    # -pr 1 = 25 cells of 0.04: thousands of cell pairs lie at the radius (7-24-25, 15-20-25) or within an ulp or
+    # two of it on these inexact coordinates; at 1.5 (37.5 cells) none does
+    ("gallery_maxdist1", "gallery_empty.graph", ["-m", "VISPREP", "-pg", "0.04", "-pp", "1.32,7.24", "-pm", "-pr", "1"],
+     [], True, "(-pr restricted visibility at a tie radius)"),
     ("barnsbury_make", "barnsbury_drawing.graph", ["-m", "VISPREP", "-pg", "2", "-pp", "531000,184000", "-pm"], [], True,
      "BASELINE configs[0] VISPREP"),
     ("barnsbury_vga", "@barnsbury_make", ["-m", "VGA", "-vm", "visibility", "-vg", "-vr", "n"], VGA_VIS, True,
@@ -102,6 +108,24 @@ CASES = [
      "vga_metric_step_depth (on the made gallery map)"),
     ("sd_angular", "@gallery_one_op", ["-m", "STEPDEPTH", "-sdt", "angular", "-sdp", "3,5"],
      ["Angular Step Depth"], True, "vga_angular_step_depth (on the made gallery map)"),
+    ("maxdist1_vis_global_3", "@gallery_maxdist1", ["-m", "VGA", "-vm", "visibility", "-vg", "-vr", "3"],
+     [c + " R3" for c in VGA_VIS], True, "(VGA global 3 on the -pr 1 graph)"),
+    # the analyses on the boundary graph (1772 of 4332 cells are nodes; the re-read chunk has m_boundarygraph = 1);
+    # BOUNDARY_SDP is cell (58, 38), one of its nodes
+    ("boundary_vis_global_n", "@gallery_boundary", ["-m", "VGA", "-vm", "visibility", "-vg", "-vr", "n"], VGA_VIS, True,
+     "(VGA global n, boundary graph)"),
+    ("boundary_vis_local", "@gallery_boundary", ["-m", "VGA", "-vm", "visibility", "-vl"],
+     ["Visual Clustering Coefficient", "Visual Control", "Visual Controllability"], True, "(VGA local, boundary graph)"),
+    ("boundary_vga_metric", "@gallery_boundary", ["-m", "VGA", "-vm", "metric", "-vr", "n"],
+     ["Metric Mean Shortest-Path Angle", "Metric Mean Shortest-Path Distance", "Metric Mean Straight-Line Distance",
+      "Metric Node Count"], True, "(VGA metric, boundary graph)"),
+    ("boundary_sd_visual", "@gallery_boundary", ["-m", "STEPDEPTH", "-sdt", "visual", "-sdp", BOUNDARY_SDP],
+     ["Visual Step Depth"], True, "(visual step depth, boundary graph)"),
+    ("boundary_sd_metric", "@gallery_boundary", ["-m", "STEPDEPTH", "-sdt", "metric", "-sdp", BOUNDARY_SDP],
+     ["Metric Step Shortest-Path Angle", "Metric Step Shortest-Path Length", "Metric Straight-Line Distance"], True,
+     "(metric step depth, boundary graph)"),
+    ("boundary_sd_angular", "@gallery_boundary", ["-m", "STEPDEPTH", "-sdt", "angular", "-sdp", BOUNDARY_SDP],
+     ["Angular Step Depth"], True, "(angular step depth, boundary graph)"),
     # turns_connected without its merge links: VISPREP -pu -pl, then -pm
     ("turns_unlink", "turns_connected.graph", ["-m", "VISPREP", "-pu", "-pl"], [], False, "(-pu -pl unmake + unlink)"),
     ("turns_remake", "@turns_unlink", ["-m", "VISPREP", "-pm"], [], True, "(remake after unlink)"),
@@ -197,11 +221,12 @@ CASES = [
 ]
 
 
-# Cases the engine refuses (DMX_ERR_UNSUPPORTED): a source of VGA global with a radius finds a context-filled
-# odd cell (not expanded) and its linked cell at one level, and the reference counts the first or extracts it
-# depending on which end it pops first inside the level (vgavisualglobal.cpp:99-122).  The reference's output
-# is kept: tests/test_semifill.py shows with the oracle that it changes with that order.
-REFUSED = {"link_vis_global_3": "merge links on context-filled cells"}
+# Cases the engine refuses (DMX_ERR_UNSUPPORTED), name -> the reason its message gives: none.  link_vis_global_3 was
+# one (a source of VGA global with a radius finds a context-filled odd cell, not expanded, and its linked cell at one
+# level, and the reference counts the first or extracts it depending on which end it pops first,
+# vgavisualglobal.cpp:99-122); the engine now runs such sources in the reference's order, and tests/test_semifill.py
+# shows with the oracle that the result changes with that order.
+REFUSED = {}
 
 
 def _pencil_args(graph):
@@ -253,6 +278,12 @@ def main():
             subprocess.check_call([REF_CLI, "-f", src, "-o", dst] + args, stdout=subprocess.DEVNULL)
             outputs[name] = dst
             b = open(dst, "rb").read()
+            if name == "gallery_boundary":
+                pm = gu.load_pointmap(dst)
+                x, y = (float(v) for v in BOUNDARY_SDP.split(","))
+                px = int(np.floor((x - pm["bottom_left"][0] + GALLERY_S / 2) / GALLERY_S))
+                py = int(np.floor((y - pm["bottom_left"][1] + GALLERY_S / 2) / GALLERY_S))
+                assert pm["state"][px * pm["rows"] + py] & 0x2, "BOUNDARY_SDP is not a node of the boundary graph"
             m = {"input": inp, "args": args, "gpu": gpu, "regression": regression, "size": len(b),
                  "sha256": hashlib.sha256(b).hexdigest(), "columns": cols}
             if name in REFUSED:

@@ -165,6 +165,8 @@ def test_maxdist_and_radius_match_oracle(ctx):
     got = g.copy()
     np.testing.assert_array_equal(got["bins"], ref["bins"])
     np.testing.assert_array_equal(got["runs"], ref["runs"])
+    np.testing.assert_array_equal(got["attrs"].view(np.uint32), ref["attrs"].view(np.uint32))
+    np.testing.assert_array_equal(got["gridconn"], ref["gridconn"])
     for r in (1, 2, 3):
         _assert_vga_close(g.vga_visual_global(radius=r), om.vga_global(radius=r))
 
