@@ -56,6 +56,10 @@ SIGNATURES = {
     "dmx_graph_connections": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp]),
     "dmx_graph_connections_csv": (_i32, [_vp, _vp, _i64, _i64, _cs, _vp, _vp, _i64, _vp]),
     "dmx_ctx_last_connections": (_i32, [_vp, _vp, _vp, _vp]),
+    "dmx_agent_schedule": (_i32, [_vp, ctypes.c_uint32, _i32, _dbl, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "dmx_agents": (_i32, [_vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64]),
+    "dmx_ctx_last_agents": (_i32, [_vp, _vp, _vp]),
+    "dmx_ctx_last_agents_detail": (_i32, [_vp, _vp, _vp]),
     "dmx_vga_isovist": (_i32, [_vp, _vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "dmx_ctx_last_isovist": (_i32, [_vp, _vp, _vp, _vp]),
     "dmx_isovists": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),

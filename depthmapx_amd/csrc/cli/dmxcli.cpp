@@ -1049,6 +1049,228 @@ struct Export : Mode {
     }
 };
 
+// AgentParser (agentparser.cpp:30-346) + runAgentAnalysis (runmethods.cpp:483-633) for the standard agents.  The
+// other ten -am modes, -ot trails and -atrails parse and are refused when run (trails need the ShapeMap writer).
+// -aseed <n> (this tool's own flag) seeds the release ensemble: the agent is the reference's bit for bit, the
+// ensemble -- one stream per agent -- is the engine's (dmx_agent_schedule), so the counts are distributed as the
+// reference's and not equal to them.
+struct Agents : Mode {
+    enum { NONE, STANDARD, OTHER } mode = NONE;
+    std::string mode_name;
+    int timesteps = 0, fov = 0, steps = 0, life = 0, trails = -1, locseed = -1;
+    long long aseed = -1;
+    double rate = 0;
+    std::vector<std::string> points;
+    std::string point_file;
+    std::vector<std::string> outputs;   // "graph", "gatecounts", "trails" in the order given
+    std::vector<std::pair<double, double>> release;
+    std::string name() const override { return "AGENTS"; }
+    static int number(const char* flag, const char* v, const char* what) {
+        if (!has_only_digits(v)) throw CommandLineException(std::string(flag) + what + v);
+        const int n = std::atoi(v);
+        if (n <= 0) throw CommandLineException(std::string(flag) + what + v);
+        return n;
+    }
+    void parse(int argc, char** argv) override {
+        for (int i = 1; i < argc;) {
+            if (!std::strcmp("-am", argv[i])) {
+                if (mode != NONE) throw CommandLineException("-am can only be used once, modes are mutually exclusive");
+                enforce_argument("-am", i, argc, argv);
+                static const char* others[] = {"los-length", "occ-length", "occ-any", "occ-group-45", "occ-group-60",
+                                               "occ-furthest", "bin-far-dist", "bin-angle", "bin-far-dist-angle",
+                                               "bin-memory"};
+                mode_name = argv[i];
+                if (mode_name == "standard") mode = STANDARD;
+                for (const char* o : others)
+                    if (mode_name == o) mode = OTHER;
+                if (mode == NONE) throw CommandLineException(std::string("Invalid AGENTS mode: ") + argv[i]);
+            } else if (!std::strcmp(argv[i], "-ats")) {
+                if (timesteps > 0) throw CommandLineException("-ats can only be used once");
+                enforce_argument("-ats", i, argc, argv);
+                timesteps = number("-ats", argv[i], " must be a number >0, got ");
+            } else if (!std::strcmp(argv[i], "-arr")) {
+                if (rate > 0) throw CommandLineException("-arr can only be used once");
+                enforce_argument("-arr", i, argc, argv);
+                if (!has_only_digits_dots_commas(argv[i]))
+                    throw CommandLineException(std::string("-arr must be a number >0, got ") + argv[i]);
+                rate = std::atof(argv[i]);
+                if (rate <= 0) throw CommandLineException(std::string("-arr must be a number >0, got ") + argv[i]);
+            } else if (!std::strcmp(argv[i], "-atrails")) {
+                if (trails >= 0) throw CommandLineException("-atrails can only be used once");
+                enforce_argument("-atrails", i, argc, argv);
+                if (!has_only_digits(argv[i]))
+                    throw CommandLineException(std::string("-atrails must be a number >=1 or 0 for all (max possible = 50), got ") + argv[i]);
+                trails = std::atoi(argv[i]);
+                if (trails < 0)
+                    throw CommandLineException(std::string("-atrails must be a number >=1 or 0 for all (max possible = 50), got ") + argv[i]);
+            } else if (!std::strcmp(argv[i], "-afov")) {
+                if (fov > 0) throw CommandLineException("-afov can only be used once");
+                enforce_argument("-afov", i, argc, argv);
+                if (!has_only_digits(argv[i]))
+                    throw CommandLineException(std::string("-afov must be a number between 1 and 32, got ") + argv[i]);
+                fov = std::atoi(argv[i]);
+                if (fov <= 0 || fov > 32)
+                    throw CommandLineException(std::string("-afov must be a number between 1 and 32, got ") + argv[i]);
+            } else if (!std::strcmp(argv[i], "-asteps")) {
+                if (steps > 0) throw CommandLineException("-asteps can only be used once");
+                enforce_argument("-asteps", i, argc, argv);
+                steps = number("-asteps", argv[i], " must be a number >0, got ");
+            } else if (!std::strcmp(argv[i], "-alife")) {
+                if (life > 0) throw CommandLineException("-alife can only be used once");
+                enforce_argument("-alife", i, argc, argv);
+                life = number("-alife", argv[i], " must be a number >0, got ");
+            } else if (!std::strcmp(argv[i], "-aseed")) {
+                if (aseed >= 0) throw CommandLineException("-aseed can only be used once");
+                enforce_argument("-aseed", i, argc, argv);
+                if (!has_only_digits(argv[i]) || std::strlen(argv[i]) > 10 || std::atoll(argv[i]) > 0xFFFFFFFFll)
+                    throw CommandLineException(std::string("-aseed must be a number between 0 and 4294967295, got ") + argv[i]);
+                aseed = std::atoll(argv[i]);
+            } else if (!std::strcmp(argv[i], "-alocseed")) {
+                if (!point_file.empty()) throw CommandLineException("-alocseed cannot be used together with -alocfile");
+                if (!points.empty()) throw CommandLineException("-alocseed cannot be used together with -aloc");
+                enforce_argument("-alocseed", i, argc, argv);
+                if (!has_only_digits(argv[i]))
+                    throw CommandLineException(std::string("Invalid starting location seed provided (") + argv[i] +
+                                               "). Should only contain digits");
+                const double v = std::atof(argv[i]);
+                if (v < 0 || v > 10)
+                    throw CommandLineException(std::string("-alocseed must be a number between 0 and 10, got ") + argv[i]);
+                locseed = (int)v;
+            } else if (!std::strcmp(argv[i], "-alocfile")) {
+                if (!points.empty()) throw CommandLineException("-alocfile cannot be used together with -aloc");
+                if (locseed > -1) throw CommandLineException("-alocfile cannot be used together with -alocseed");
+                enforce_argument("-alocfile", i, argc, argv);
+                point_file = argv[i];
+            } else if (!std::strcmp(argv[i], "-aloc")) {
+                if (!point_file.empty()) throw CommandLineException("-aloc cannot be used together with -alocfile");
+                if (locseed > -1) throw CommandLineException("-aloc cannot be used together with -alocseed");
+                enforce_argument("-aloc", i, argc, argv);
+                if (!has_only_digits_dots_commas(argv[i]))
+                    throw CommandLineException(std::string("Invalid starting point provided (") + argv[i] +
+                                               "). Should only contain digits dots and commas");
+                points.push_back(argv[i]);
+            } else if (!std::strcmp(argv[i], "-ot")) {
+                enforce_argument("-ot", i, argc, argv);
+                for (const char* t : {"graph", "gatecounts", "trails"})
+                    if (!std::strcmp(argv[i], t)) {
+                        if (std::find(outputs.begin(), outputs.end(), t) != outputs.end())
+                            throw CommandLineException(std::string("Same output type argument (") + t + ") provided twice");
+                        outputs.push_back(t);
+                    }
+            }
+            ++i;
+        }
+        if (mode == NONE) mode = STANDARD;
+        if (timesteps == 0) throw CommandLineException("Total number of timesteps (-ats <timesteps>) is required");
+        if (rate == 0) throw CommandLineException("Release rate (-arr <rate>) is required");
+        if (fov == 0) throw CommandLineException("Agent field-of-view (-afov <bins>) is required");
+        if (steps == 0)
+            throw CommandLineException("Agent number of steps before turn decision (-asteps <steps>) is required");
+        if (life == 0) throw CommandLineException("Agent life in timesteps (-alife <timesteps>) is required");
+        if (point_file.empty() && points.empty() && locseed == -1)
+            throw CommandLineException("Either -aloc, -alocfile or -alocseed must be given");
+        if (!point_file.empty() || !points.empty()) release = points_from_args(points, point_file);
+    }
+    void run(const Args& a, Perf& perf) override {
+        Document d;
+        const auto t0 = std::chrono::steady_clock::now();
+        read_document(a.file, d);
+        const auto t1 = std::chrono::steady_clock::now();
+        if (mode == OTHER)
+            throw RuntimeException("Agent mode " + mode_name + " is not part of the accelerated path: only -am standard is");
+        if (trails >= 0 || std::find(outputs.begin(), outputs.end(), "trails") != outputs.end())
+            throw RuntimeException("Agent trails (-atrails, -ot trails) need a shape map writer: they are not part of the "
+                                   "accelerated path");
+        Context C;
+        LoadedMap m;
+        const auto t2 = std::chrono::steady_clock::now();
+        load_map(C, d, m);
+        perf.add("Load graph file", std::chrono::duration<double>((t1 - t0) + (std::chrono::steady_clock::now() - t2)).count());
+        int processed = 0;
+        check(dmx_chunk_flags(m.chunk, &processed, nullptr, nullptr, nullptr));
+        if (!processed) throw RuntimeException("The map has no visibility graph: run VISPREP -pm first");
+        int32_t cols = 0, rows = 0;
+        double blx = 0, bly = 0, sp = 0;
+        check(dmx_pointmap_info(m.pm, &cols, &rows, &blx, &bly, nullptr));
+        check(dmx_chunk_info(m.chunk, nullptr, nullptr, &sp, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+        // release points -> cells: PointMap::pixelate(point, false) (runmethods.cpp:549-552)
+        std::vector<int32_t> cells;
+        for (auto& p : release) {
+            const double fx = std::floor((p.first - blx + (sp / 2.0)) / sp), fy = std::floor((p.second - bly + (sp / 2.0)) / sp);
+            if (!(fx >= 0 && fx < cols && fy >= 0 && fy < rows))
+                throw RuntimeException("A release point lies outside the map's grid");
+            cells.push_back((int32_t)fx * rows + (int32_t)fy);
+        }
+        std::cout << "ok\nRunning agent analysis... " << std::flush;
+        std::vector<uint32_t> counts((size_t)cols * rows, 0u);
+        timed(perf, "Running agent analysis", [&] {
+            const uint32_t seed = aseed < 0 ? 0u : (uint32_t)aseed;
+            int64_t n = 0;
+            check(dmx_agent_schedule(m.pm, seed, timesteps, rate, life, cells.data(), (int64_t)cells.size(),
+                                     locseed < 0 ? 0 : locseed, nullptr, nullptr, nullptr, 0, &n));
+            std::vector<int32_t> cell((size_t)std::max<int64_t>(n, 1)), moves((size_t)std::max<int64_t>(n, 1));
+            std::vector<uint32_t> seeds((size_t)std::max<int64_t>(n, 1));
+            check(dmx_agent_schedule(m.pm, seed, timesteps, rate, life, cells.data(), (int64_t)cells.size(),
+                                     locseed < 0 ? 0 : locseed, cell.data(), seeds.data(), moves.data(), n, &n));
+            // runmethods.cpp:499-504
+            check(dmx_agents(C.ctx, m.g, fov == 32 ? -1 : (fov - 1) / 2, steps, n, cell.data(), seeds.data(), moves.data(),
+                             counts.data(), nullptr, nullptr, nullptr, nullptr, 0));
+        });
+        // "Gate Counts" as AgentEngine::run and Agent::onMove leave it: getOrInsertColumn (a new column holds -1),
+        // then incrValue per visit (attributetable.cpp:212-225: a negative value becomes the increment, else it is
+        // added to); sequential float increments stop at 2^24.  The column becomes the displayed attribute.
+        {
+            int32_t ncols = 0;
+            check(dmx_chunk_info(m.chunk, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ncols, nullptr, nullptr));
+            std::vector<float> old((size_t)m.nnodes, -1.0f);
+            for (int i = 0; i < ncols; i++) {
+                char nm[1024] = {0};
+                check(dmx_chunk_column(m.chunk, i, nm, (int)sizeof(nm), nullptr, nullptr));
+                if (!std::strcmp(nm, "Gate Counts")) check(dmx_chunk_column(m.chunk, i, nm, (int)sizeof(nm), old.data(), nullptr));
+            }
+            std::vector<int32_t> st((size_t)cols * rows);
+            check(dmx_pointmap_state(m.pm, st.data()));
+            std::vector<float> v((size_t)m.nnodes);
+            std::vector<uint8_t> set((size_t)m.nnodes);
+            int64_t k = 0;
+            for (int64_t c = 0; c < (int64_t)st.size() && k < m.nnodes; c++) {
+                if (!(st[c] & 0x2)) continue;   // Point::FILLED; nodes are the filled cells, x-major
+                const double cnt = (double)counts[(size_t)c], o = (double)old[k];
+                double nv = o;
+                if (cnt > 0) nv = o < 0 ? std::min(cnt, 16777216.0) : std::min(o + cnt, std::max(o, 16777216.0));
+                v[k] = (float)nv;
+                set[k] = (cnt > 0 || old[k] != -1.0f) ? 1 : 0;
+                k++;
+            }
+            m.column("Gate Counts", v.data(), set.data(), false, true);
+        }
+        std::cout << " ok\nWriting out result..." << std::flush;
+        auto write_graph = [&](const std::string& path) {
+            timed(perf, "Writing graph", [&] {
+                d.put_displayed(m.bytes(), false);
+                write_document(path, d);
+            });
+        };
+        auto write_gatecounts = [&](const std::string& path) {
+            timed(perf, "Writing gatecounts", [&] {
+                const std::vector<uint8_t> bytes = m.bytes();
+                dmx_chunk* ch = nullptr;
+                check(dmx_chunk_parse(bytes.data(), (int64_t)bytes.size(), &ch));
+                std::unique_ptr<dmx_chunk, int (*)(dmx_chunk*)> guard(ch, dmx_chunk_free);
+                Export::write_file(path, Export::data_csv(ch));   // outputSummary(stream, ',')
+            });
+        };
+        const bool graph = std::find(outputs.begin(), outputs.end(), "graph") != outputs.end();
+        if (outputs.empty() || (outputs.size() == 1 && graph)) write_graph(a.out);
+        else if (outputs.size() == 1) write_gatecounts(a.out);
+        else {
+            if (graph) write_graph(a.out + ".graph");
+            write_gatecounts(a.out + "_gatecounts.csv");
+        }
+        std::cout << " ok" << std::endl;
+    }
+};
+
 void print_help() {
     std::cout << "Usage: dmxcli -m <mode> -f <filename> -o <output file> [-t <times.csv>] [-s] [-p] [mode options]\n"
                  "Modes (the accelerated depthmapXcli path):\n"
@@ -1057,6 +1279,11 @@ void print_help() {
                  "  STEPDEPTH -sdt metric|visual|angular -sdp <x,y> | -sdf <points file>\n"
                  "  EXPORT    -em pointmap-data-csv | pointmap-connections-csv | pointmap-links-csv\n"
                  "            (the displayed point map as CSV; -o names the CSV file)\n"
+                 "  AGENTS    [-am standard] -ats <timesteps> -arr <release rate> -afov <bins 1..32> -asteps <steps>\n"
+                 "            -alife <timesteps> -alocseed <0..10> | -aloc <x,y> ... | -alocfile <points file>\n"
+                 "            [-aseed <ensemble seed>] [-ot graph] [-ot gatecounts]\n"
+                 "            (standard agents, \"Gate Counts\"; the agent is the reference's, the release ensemble\n"
+                 "            is seeded per agent, so counts are distributed as depthmapXcli's, not equal to them)\n"
                  "Input: a depthmapX .graph (written back as .graph), or a CSV drawing (x1,y1,x2,y2) / a .dmxg\n"
                  "written by this tool (written as .dmxg)\n";
 }
@@ -1069,6 +1296,7 @@ int main(int argc, char* argv[]) {
     modes.emplace_back(new Vga());
     modes.emplace_back(new StepDepth());
     modes.emplace_back(new Export());
+    modes.emplace_back(new Agents());
     try {
         // CommandLineParser::parse (commandlineparser.cpp:51-133)
         if (argc <= 1) throw CommandLineException("No commandline parameters provided - don't know what to do");

@@ -42,6 +42,7 @@
 #include "kernels/isovist_points.hip"
 #include "kernels/chunk_codec.hip"
 #include "kernels/connections.hip"
+#include "kernels/agents.hip"
 
 using namespace dmx;
 
@@ -223,6 +224,9 @@ struct dmx_ctx {
     double last_conn_s[2] = {0, 0};          // connections: counting pass and scan, emitting pass (kernels)
     long long last_conn[4] = {0, 0, 0, 0};   // connections: bitmap in HBM, nodes with duplicates, cells dropped as
                                              // duplicates, cells dropped outside the grid
+    double last_agents_s = 0, last_agents_host_s = 0;   // agents: kernel seconds, seconds of the host re-runs
+    long long last_agents[7] = {};           // agents: moves, looks, host re-runs, bins clamped, whole-isovist
+                                             // fallbacks, diagonal steps taken, moves stopped
 };
 
 struct dmx_pointmap {
@@ -734,6 +738,7 @@ int dmx_ctx_last_timing(dmx_ctx* c, double* mk, double* vga) {
 #include "api/vga_other.hip"
 #include "api/thruvision.hip"
 #include "api/connections.hip"
+#include "api/agents.hip"
 #include "api/isovist.hip"
 #include "api/isovist_points.hip"
 #include "api/stepdepth.hip"

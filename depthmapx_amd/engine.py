@@ -167,6 +167,19 @@ class Context:
         return dict(count_seconds=c.value, emit_seconds=e.value, bitmap_hbm=int(d[0]), dup_nodes=int(d[1]),
                     dup_cells=int(d[2]), outside_cells=int(d[3]))
 
+    def last_agents(self):
+        """The last Graph.agents (dmx_ctx_last_agents, dmx_ctx_last_agents_detail): kernel seconds, the moves made
+        (Agent::onStep calls), the looks, the agents run again on the host (a look within 1e-9 of a bin boundary) and
+        the bins clamped (a draw beyond the cells a bin's runs enumerate: re-read maps only); the seconds of those
+        host re-runs, the narrow looks that fell back to the whole isovist, the diagonal steps taken and the moves
+        that stopped."""
+        t, ht = ctypes.c_double(), ctypes.c_double()
+        d, e = np.zeros(4, dtype=np.int64), np.zeros(3, dtype=np.int64)
+        N.check(N.lib().dmx_ctx_last_agents(self.h, ctypes.byref(t), N.ptr(d)))
+        N.check(N.lib().dmx_ctx_last_agents_detail(self.h, ctypes.byref(ht), N.ptr(e)))
+        return dict(seconds=t.value, moves=int(d[0]), looks=int(d[1]), host_reruns=int(d[2]), clamped=int(d[3]),
+                    host_seconds=ht.value, fallbacks=int(e[0]), diag_taken=int(e[1]), stopped=int(e[2]))
+
     ISOVIST_POLY_GUESS = 128   # vertices a point the first call with polygons=True makes room for
 
     def isovists(self, lines, points, angles=None, region=None, simple=False, polygons=False):
@@ -335,6 +348,23 @@ class PointMap:
         arr = np.ascontiguousarray(cell_pairs, dtype=np.int32).reshape(-1, 2)
         N.check(N.lib().dmx_pointmap_set_merges(self.h, N.ptr(arr), len(arr)))
 
+    def agent_schedule(self, seed=0, timesteps=5000, release_rate=0.1, lifetime=1000, release_cells=None, locseed=0):
+        """The release table of an agent analysis (dmx_agent_schedule; AgentEngine::run's release loop and
+        AgentSet::init over two streams of this engine's own): int32 [n][3] rows (start cell x-major, agent seed,
+        moves).  release_cells: x-major cells agents start from; None or empty: random filled cells from the stream
+        seeded locseed.  The defaults are the reference's (5000 timesteps, 0.1 agents a timestep, 1000 steps of
+        life)."""
+        rel = np.ascontiguousarray([] if release_cells is None else release_cells, dtype=np.int32).reshape(-1)
+        n = ctypes.c_int64()
+        args = (self.h, int(seed) & 0xFFFFFFFF, int(timesteps), float(release_rate), int(lifetime), N.ptr(rel), len(rel),
+                int(locseed))
+        N.check(N.lib().dmx_agent_schedule(*args, None, None, None, 0, ctypes.byref(n)))
+        cell = np.zeros(max(n.value, 1), dtype=np.int32)
+        aseed = np.zeros(max(n.value, 1), dtype=np.uint32)
+        moves = np.zeros(max(n.value, 1), dtype=np.int32)
+        N.check(N.lib().dmx_agent_schedule(*args, N.ptr(cell), N.ptr(aseed), N.ptr(moves), n.value, ctypes.byref(n)))
+        return np.stack([cell, aseed.view(np.int32), moves], axis=1)[:n.value]
+
     def make_graph(self, ctx, boundarygraph=False, maxdist=-1.0, node_begin=0, node_end=-1):
         h = ctypes.c_void_p()
         N.check(N.lib().dmx_makegraph(ctx.h, self.h, float(maxdist), int(bool(boundarygraph)), int(node_begin),
@@ -502,6 +532,32 @@ class Graph:
         N.check(N.lib().dmx_vga_thruvision(self.ctx.h, self.h, int(src_begin), int(src_end), N.ptr(out),
                                            N.ptr(cnt)))
         return (out, cnt) if counts else out
+
+    def agents(self, table, fov=15, steps=3, trails=0):
+        """The agent analysis with standard agents on the GPU (dmx_agents): every agent of `table` (int32 [n][3]:
+        start cell, seed, moves -- PointMap.agent_schedule) as the reference's Agent after pafsrand(seed).  fov: bins
+        of the field of view (32: the whole isovist; runmethods.cpp:499-504), steps: AgentProgram::m_steps.  Returns
+        dict(counts uint32 [cols*rows] x-major -- what the agents add to "Gate Counts" --, final_cell int32 [n],
+        final_loc float64 [n][2], stuck uint8 [n], trails int32 [trails][max moves]: the cell after each move of
+        the first `trails` agents, -1 beyond an agent's moves)."""
+        table = np.ascontiguousarray(table, dtype=np.int32).reshape(-1, 3)
+        n = len(table)
+        cell = np.ascontiguousarray(table[:, 0])
+        seed = np.ascontiguousarray(table[:, 1]).view(np.uint32)
+        moves = np.ascontiguousarray(table[:, 2])
+        i = self.pm.info()
+        vbin = -1 if int(fov) == 32 else (int(fov) - 1) // 2
+        counts = np.zeros(i["cols"] * i["rows"], dtype=np.uint32)
+        final_cell = np.zeros(n, dtype=np.int32)
+        final_loc = np.zeros((n, 2), dtype=np.float64)
+        stuck = np.zeros(n, dtype=np.uint8)
+        ntrail = min(int(trails), n)
+        trail = np.full((ntrail, int(moves.max()) if n else 0), -1, dtype=np.int32) if ntrail else None
+        N.check(N.lib().dmx_agents(self.ctx.h, self.h, vbin, int(steps), n, N.ptr(cell), N.ptr(seed), N.ptr(moves),
+                                   N.ptr(counts), N.ptr(final_cell), N.ptr(final_loc), N.ptr(stuck), N.ptr(trail),
+                                   ntrail))
+        return dict(counts=counts, final_cell=final_cell, final_loc=final_loc, stuck=stuck,
+                    trails=trail if ntrail else np.zeros((0, 0), dtype=np.int32))
 
     def _node_range(self, node_begin, node_end):
         nb, ne = int(node_begin), int(node_end)

@@ -295,6 +295,56 @@ int dmx_graph_connections_csv(dmx_ctx* ctx, dmx_graph* g, int64_t node_begin, in
  * whose bitmap does not fit LDS; 0: in LDS), nodes that held a duplicate, cells dropped as duplicates, cells dropped
  * outside the grid}.  Any pointer may be NULL. */
 int dmx_ctx_last_connections(dmx_ctx* ctx, double* count_s, double* emit_s, int64_t* out4);
+/* ---- Agent analysis: standard agents, Gate Counts (GPU) ----------------------------------------- */
+/* depthmapXcli -m AGENTS with the standard look (salalib/agents/: AgentEngine::run, AgentSet, Agent; SEL_STANDARD).
+ * The reference draws every agent's numbers from one global generator, so its run is one sequential stream.  Agents
+ * never interact; here every agent owns a stream (the reference's 64-bit LCG, seeded as pafsrand(seed) seeds it), and
+ * the AGENT is the reference's bit for bit: after pafsrand(agent_seed) a reference Agent on the same graph walks the
+ * same cells to the same final location.  The ENSEMBLE (who is released when, where and with which seed) is this
+ * engine's, so a run here and a run of the reference hold different, equally distributed counts.
+ *
+ * dmx_agent_schedule (host only) restates AgentEngine::run's release loop (agentengine.cpp:66-84) and AgentSet::init
+ * (agentset.cpp:28-40) over two streams of its own.  The stream seeded `seed` gives, per timestep, the count
+ * invcumpoisson(prandomr(), release_rate) and, per agent, its seed (the stream's next pafrand) and -- with release
+ * cells -- pafrand() % nrelease.  Without release cells a stream seeded `locseed` repeats pickPixel(prandom())
+ * (pointdata.cpp:1771-1775) until the cell is FILLED; a draw of exactly 0 is drawn again (the reference indexes
+ * cell -1 there).  moves = min(lifetime, timesteps - release timestep).  Cells are x-major indices.  *nagents
+ * receives the number of agents; the first cap are written (cap 0: count only).  A release cell outside the grid
+ * or not FILLED: DMX_ERR_ARG; a map without FILLED cells and without release cells: DMX_ERR_STATE. */
+int dmx_agent_schedule(const dmx_pointmap* pm, uint32_t seed, int32_t timesteps, double release_rate,
+                       int32_t lifetime, const int32_t* release_cells, int64_t nrelease, int32_t locseed,
+                       int32_t* start_cell, uint32_t* agent_seed, int32_t* moves, int64_t cap, int64_t* nagents);
+/* Every agent of the table from Agent::onInit(start) through moves[i] x Agent::onMove, on the GPU.  vbin is
+ * AgentProgram::m_vbin (-1: the whole isovist; runmethods.cpp:499-504 derives it from the field of view), steps
+ * m_steps.  The graph must hold every node.
+ *   counts      host [cols*rows], x-major: per cell, the moves that entered it from another cell while it is FILLED
+ *               (what the reference adds to "Gate Counts").  Written, not added to; sums of calls over disjoint parts
+ *               of a table equal the whole table's, in any order.
+ *   final_cell  host [n], final_loc host [n][2], stuck host [n]: m_node, m_loc, m_stuck after the last move (optional)
+ *   trail       host [ntrail][max of moves] or NULL: the cell after each move of the first ntrail agents, -1 beyond
+ *               an agent's moves
+ * Defined where the reference is not: an agent whose look finds no cell even in the whole isovist is stuck for good
+ * and counts nothing more; a draw beyond the cells a bin's runs enumerate (re-read maps only) takes the bin's last
+ * cell and is reported by dmx_ctx_last_agents.  binfromvec needs acos, whose last bit may differ between device and
+ * host: an agent whose look lies within 1e-9 of a bin boundary is run again on the host (reported as well).
+ * Progress and cancel as in dmx_vga_thruvision (phase DMX_PHASE_VGA; the unit is 64 agents).
+ * Test and measurement hook: with the environment variable DMX_AGENTS_HOST set, the call launches no kernel and runs
+ * EVERY agent through that host routine on one thread ("lazy": the run pool read a bin at a time, as for a flagged
+ * agent; any other value: the whole pool downloaded first).  The results are the same; dmx_ctx_last_agents then
+ * reports every agent as run again on the host.  Leave it unset in production. */
+int dmx_agents(dmx_ctx* ctx, dmx_graph* g, int32_t vbin, int32_t steps, int64_t nagents,
+               const int32_t* start_cell, const uint32_t* agent_seed, const int32_t* moves,
+               uint32_t* counts /* [cols*rows], x-major */, int32_t* final_cell, double* final_loc /* [n][2] */,
+               uint8_t* stuck, int32_t* trail /* [ntrail][max moves] or NULL */, int64_t ntrail);
+/* The last dmx_agents call: kernel seconds and out4 = {moves made (Agent::onStep calls), looks, agents run again on
+ * the host, bins clamped}.  Any pointer may be NULL. */
+int dmx_ctx_last_agents(dmx_ctx* ctx, double* seconds, int64_t* out4);
+/* More of the same call: the seconds the host routine spent on the agents run again (without the download of the
+ * graph's per-node arrays that the first of them costs: cell map, grid connections, bin counts, run counts, run starts;
+ * with the reads of the run pool, a bin at a time as the looks need it), and out3 =
+ * {narrow looks that fell back to the whole isovist, diagonal steps taken, moves that stopped (both diagonal tries
+ * refused)}.  Any pointer may be NULL. */
+int dmx_ctx_last_agents_detail(dmx_ctx* ctx, double* host_seconds, int64_t* out3);
 /* ---- VGA isovist analysis (GPU) -------------------------------------------------------------- */
 /* MetaGraph::analyseGraph(OUTPUT_ISOVIST) -> VGAIsovist().run (salalib/mgraph.cpp:346-348,
  * vgamodules/vgaisovist.cpp:24-129; what depthmapXcli -m VGA runs without -vm): a BSP tree of the drawing lines
