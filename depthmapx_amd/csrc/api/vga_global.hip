@@ -98,7 +98,7 @@ static int build_scan_order(dmx_graph* g) {
 static int restore_scan_order(dmx_graph* g) {
     if (!g->scan_released) return DMX_OK;
     g->pmask.reset(); g->ppre.reset(); g->poff.reset();
-    g->tvis.reset(); g->ftvis.reset(); g->tvsum.reset(); g->tvnz.reset(); g->ttvis.reset();
+    g->tvis.reset(); g->ftvis.reset(); g->tvsum.reset(); g->tvnz.reset(); g->tvblk.reset(); g->ttvis.reset();
     g->tvw = 0;
     g->tiles_ready = false;
     return build_scan_order(g);
@@ -333,7 +333,8 @@ static void prep_state_stats(dmx_ctx* ctx, const dmx_graph* g) {
     if (g->tvsum.p || g->tvnz.p) f |= 64;   // row summaries
     ctx->last_stats[40] = f;
     ctx->last_stats[41] = (long long)((g->tvis.p ? g->tvis.n * 8 : 0) + (g->ftvis.p ? g->ftvis.n * 8 : 0) +
-                                      (g->ttvis.p ? g->ttvis.n * 8 : 0) + (g->tvsum.p ? g->tvsum.n * 8 : 0) + (g->tvnz.p ? g->tvnz.n * 8 : 0));
+                                      (g->ttvis.p ? g->ttvis.n * 8 : 0) + (g->tvsum.p ? g->tvsum.n * 8 : 0) + (g->tvnz.p ? g->tvnz.n * 8 : 0) +
+                                      (g->tvblk.p ? g->tvblk.n * 8 : 0));
     ctx->last_stats[42] = (long long)(g->scan_pool.p ? g->scan_pool.n * sizeof(Run) : 0);
 }
 
@@ -487,6 +488,17 @@ static int prepare_tiles(dmx_graph* g) {
                                g->tvnz.p);
             HIPCHK(hipGetLastError());
         }
+        // narrow grids with the masks: every cell's view by 8 x 8 blocks of tiles, 4 words (32 B) a cell: phase C's miss
+        // certificate reads them a chunk of hard cells at once, in front of the rows (the rows are already
+        // all-reduced under a prep shard).  The summary holds 256 blocks: every square grid of up to 256 row words fits
+        // (1024 cells a side are 16 x 16), a few elongated ones do not (three row words a tile row over 85 tile rows are
+        // 24 x 11 = 264 blocks) and run without the certificate.
+        if (!wide && ftv && g->pmask.p && ((tw + 7) / 8) * ((th + 7) / 8) <= 256) {
+            HIPCHK(g->tvblk.alloc((size_t)Ct * 4));
+            hipLaunchKernelGGL(tile_vblk_kernel, dim3((unsigned)((Ct + 3) / 4)), dim3(256), 0, s, Ct, tvw, (tw + 63) / 64,
+                               (tw + 7) / 8, g->tvis.p, g->tvblk.p);
+            HIPCHK(hipGetLastError());
+        }
         g->tvw = tvw;
     }
     HIPCHK(hipStreamSynchronize(s));
@@ -605,6 +617,7 @@ static int launch_tile(dmx_ctx* ctx, const VgaTileParams& Q, int64_t nsrc, size_
         else if (Q.tvis && Q.tvw != Q.th * ((Q.tw + 63) / 64)) why = "tile-visibility row width differs from the tile grid";
         else if (!FG && Q.pmask && Q.tvw > 256) why = "row words past the fused phase-C test (256)";
         else if (Q.tvnz && (FG || Q.tvw > 256)) why = "narrow row summaries on a wide grid";
+        else if (Q.tvblk && (FG || ((Q.tw + 7) / 8) * ((Q.th + 7) / 8) > 256)) why = "tile-block summaries past 256 blocks";
         else if (Q.pmask && !FG && nt > 32767) why = "narrow mask hint: tile index above 15 bits";
         else if (Q.asym_tiles && Q.alist_cap <= 0) why = "asymmetric mode without an A-cell list";
         if (why) return fail(DMX_ERR_STATE, (std::string("VGA tile launch: ") + why).c_str());
@@ -666,6 +679,7 @@ static int launch_tile(dmx_ctx* ctx, const VgaTileParams& Q, int64_t nsrc, size_
     P.bsplit = policy::hook_int("DMX_VGA_BSPLIT", policy::kVgaTileBSplit) & 3;
     P.csplit = policy::hook_int("DMX_VGA_CSPLIT", policy::kVgaTileCSplit) & 1;
     P.walk = policy::hook_int("DMX_VGA_WALK", policy::kVgaTileWalk) != 0;
+    P.ccert = policy::hook_int("DMX_VGA_CCERT", policy::kVgaTileCCert) != 0;
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     P.ctl = ctx->d_ctl;
     ctx->h_ctl->progress = 0;
@@ -709,6 +723,7 @@ static int vga_tile_impl(dmx_ctx* ctx, dmx_graph* g, double radius, int gates_on
     Q.tvis = g->tvw ? g->tvis.p : nullptr; Q.tvw = g->tvw;
     Q.tvsum = (g->tvw && g->tvsum.p) ? g->tvsum.p : nullptr;
     Q.tvnz = (g->tvw && g->tvnz.p) ? g->tvnz.p : nullptr;
+    Q.tvblk = (g->tvw && g->tvblk.p) ? g->tvblk.p : nullptr;
     Q.ftvis = (g->tvw && g->ftvis.p) ? g->ftvis.p : nullptr;
     Q.ttvis = (g->tvw && g->ttvis.p) ? g->ttvis.p : nullptr;
     Q.ttany = Q.ttvis ? g->ttvis.p + (size_t)tw * th * g->tvw : nullptr;
@@ -769,6 +784,7 @@ static int vga_tile_impl(dmx_ctx* ctx, dmx_graph* g, double radius, int gates_on
     // bottom-up levels win (2000^2 interior block: alpha 60 -> 200: 2.70 -> 2.28 s, identical output;
     // 1000 and 100000 the same, profiles/r5_vga2000_alpha.jsonl)
     if (fg && !policy::hook("DMX_VGA_ALPHA")) Q.alpha = policy::kVgaTileAlphaHbm;
+    if (fg) Q.tvblk = nullptr;   // (the certificate's summaries are read with the frontier in LDS only)
     DevBuf<unsigned long long> xg;
     DevBuf<int4> queue;
     DevBuf<int32_t> list;
@@ -827,7 +843,7 @@ static int vga_tile_impl(dmx_ctx* ctx, dmx_graph* g, double radius, int gates_on
     ctx->last_stats[21] = (long long)st[19];                          // phase-B cells
     ctx->last_stats[22] = (long long)st[20];                          // phase-B tiles resolved by ttvis
     ctx->last_stats[27] = (long long)st[25];                          // phase-B tiles pruned by ttany
-    ctx->last_stats[28] = (long long)st[26];                          // phase-B row-test clocks (not collected: 0)
+    ctx->last_stats[28] = (VGA_ROWSTAT || VGA_CSTAT) ? (long long)st[26] : 0;   // phase-B row-test clocks (not collected: 0)
     ctx->last_stats[29] = (long long)st[27];                          // phase-B tiles with cell tests
     ctx->last_stats[30] = (long long)st[28];                          // phase-B cell-test clocks (not collected: 0)
     ctx->last_stats[31] = (long long)st[29];                          // phase-B cells past hint + 4 heads
@@ -837,6 +853,8 @@ static int vga_tile_impl(dmx_ctx* ctx, dmx_graph* g, double radius, int gates_on
     ctx->last_stats[25] = 0;                                          // phase-C special-node clocks (not collected: 0)
     ctx->last_stats[48] = (long long)st[23];                          // the longest tile list a walk took
     ctx->last_stats[49] = (VGA_ROWSTAT || VGA_CSTAT) ? 0 : (long long)st[22];   // phase-C cells through the row stage
+    const long long ncert = (VGA_ROWSTAT || VGA_CSTAT) ? 0 : (long long)st[26];
+    ctx->last_stats[50] = ncert;                                      // phase-C cells rejected by the miss certificate
     ctx->last_stats[26] = (long long)st[24];                          // phase-C special-node tests
     ctx->last_stats[3] = 3 | ((long long)g->nspecial << 8);
     ctx->last_stats[4] = (long long)st[0];
@@ -850,7 +868,7 @@ static int vga_tile_impl(dmx_ctx* ctx, dmx_graph* g, double radius, int gates_on
     ctx->last_stats[12] = blocks | ((long long)kt << 32) | ((long long)ntpb << 40) | ((long long)fg << 56) |
                           ((long long)rbm << 57);
     ctx->last_stats[13] = (long long)st[13];
-    ctx->last_stats[14] = (long long)st[14] * g->tvw * 8;   // bytes of tile-visibility rows read
+    ctx->last_stats[14] = ((long long)st[14] - ncert) * g->tvw * 8;   // bytes of tile-visibility rows read (not the certificate's cells')
     ctx->last_stats[15] = (long long)st[15];                          // runs scanned in phase C
     ctx->last_stats[16] = (long long)st[1];                           // phase-C cells that hit
     ctx->last_stats[17] = (long long)st[14];                          // phase-C cells (regular)
@@ -997,6 +1015,7 @@ static int vga_impl(dmx_ctx* ctx, dmx_graph* g, double radius, int gates_only, i
     ctx->last_stats[43] = 0;
     ctx->last_stats[48] = 0;   // (the tile search's longest tile list)
     ctx->last_stats[49] = 0;   // (its hard cells through the row stage)
+    ctx->last_stats[50] = 0;   // (... rejected by the miss certificate)
     PointMapHost& h = *g->pm->host;
     const int tw = (h.cols() + 7) / 8, th = (h.rows() + 7) / 8;
     const int maxlev = 4096;

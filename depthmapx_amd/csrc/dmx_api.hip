@@ -206,7 +206,7 @@ struct dmx_ctx {
     long long phase_cycles[5] = {0, 0, 0, 0, 0};   // tile BFS: level 1, A, B, C, bookkeeping (sum over workgroups)
     DevBuf<int> counters;   // [0] work counter, [1] error word, [2..3] pool cursor (u64)
     DevBuf<unsigned long long> stats; // [0..1] makegraph, [4..6] vga
-    long long last_stats[50] = {};
+    long long last_stats[51] = {};
     std::vector<int64_t> last_mk_reruns;   // sources the last makeGraph re-ran (MK_CAPACITY_TAG: capacity)
     // progress / cancel (dmx_ctx_set_progress, dmx_ctx_cancel): host-mapped block polled by the kernels
     DmxCtl* h_ctl = nullptr;
@@ -297,6 +297,7 @@ struct dmx_graph {
     DevBuf<unsigned long long> ttvis;  // tile-to-tile full visibility (AND of ftvis over regular cells)
     DevBuf<unsigned long long> tvsum;  // wide grids: per cell, one bit per non-zero tvis row word
     DevBuf<unsigned long long> tvnz;   // grids up to 256 row words: the same (phase C skips the zero words)
+    DevBuf<unsigned long long> tvblk;  // [nt*64][4] grids up to 256 row words with the masks: the cell's view by 8 x 8 blocks of tiles
     DevBuf<unsigned long long> pmask;  // partial-tile masks (the cells of each partly seen tile a cell sees)
     DevBuf<int64_t> poff;              // [Ct + 1] start of each cell's masks
     DevBuf<uint16_t> ppre;             // [Ct][tvw] partial tiles of a cell before each row word
@@ -720,7 +721,7 @@ int dmx_ctx_free(dmx_ctx* c) {
 
 int dmx_ctx_last_stats(dmx_ctx* c, int64_t* out, int n) {
     if (!c || !out) return fail(DMX_ERR_ARG, "bad arguments");
-    for (int i = 0; i < n && i < 50; i++) out[i] = c->last_stats[i];
+    for (int i = 0; i < n && i < 51; i++) out[i] = c->last_stats[i];
     return DMX_OK;
 }
 

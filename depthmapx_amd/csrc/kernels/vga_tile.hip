@@ -14,7 +14,8 @@
 //          one hit discovers all of the tile's unvisited regular cells;
 //       B. a wave per remaining tile, lane = cell: the tile-to-tile rows (ttvis / ttany), then each cell's
 //          first head runs and its hint (the run or partial-tile mask that last hit), then the other heads;
-//       C. hard cells, a wave per cell: the tile-visibility rows (tvis / ftvis) give a certain hit or miss,
+//       C. hard cells, a wave per cell: a chunk's block summaries (tvblk against fblk) first reject the cells that see
+//          no block of tiles with a frontier tile in it; the tile-visibility rows (tvis / ftvis) give a certain hit or miss,
 //          the partial-tile masks decide the rest exactly (the regular cells of a chunk in a loop of their own,
 //          c1_chunk: rows as unpredicated range-checked buffer loads, hints written once a chunk); without the
 //          masks (memory, grids above 1024 a side) the cell's runs are scanned, with the tvis rows (and their
@@ -57,6 +58,8 @@ struct VgaTileParams {
     const unsigned long long* tvsum;          // [nt*64][ceil(tvw / 64)] non-zero row words (wide grids; null: off)
     const unsigned long long* tvnz;           // [nt*64][ceil(tvw / 64)] the same on grids up to 256 row words: phase C
                                               // loads only a hard cell's non-zero row words (null: off)
+    const unsigned long long* tvblk;          // [nt*64][4] the cell's view by 8 x 8 blocks of tiles (bit (ty >> 3) * nbc +
+                                              // (tx >> 3), nbc = ceil(tw / 8)): phase C's miss certificate (null: off)
     const int32_t* node_cell;
     const int32_t* cell_node;
     const uint8_t* node_flags;
@@ -104,6 +107,7 @@ struct VgaTileParams {
     int bsplit;               // phase B in stages: bit 0 row stage + cell stage, bit 1 extension stage (0: fused)
     int csplit;               // phase C in stages: bit 0 row stage (a chunk's regular cells in a loop of their own, c1_chunk; 0: in the chunk's one loop)
     int walk;                 // the tile walks take VGA_WALK_NF tiles a thread at once, level 1 is built in place (0: a tile at a time)
+    int ccert;                // phase C rejects a chunk's certain misses from their block summaries (tvblk) before their rows (0: off)
     const int2* mpairs;      // [nmp] merge links (cell a, cell b), x-major (Point::m_merge; nullptr: none)
     int nmp;
     const int2* mamb;         // [nmamb] links with a context-filled odd end (that end first; merge_order_check)
@@ -131,6 +135,7 @@ struct VgaTileParams {
                                 // [16] phase-C hits certified by a fully seen frontier tile, [17] top-down clocks,
                                 // [18] phase-B tiles, [19] phase-B cells, [20] phase-B tiles resolved by ttvis, [25] pruned by ttany
                                 // [23] the longest tile list a level's walks took (a maximum, not a sum)
+                                // [26] hard cells rejected by the miss certificate (counted in [13] as well)
 };
 
 __device__ __forceinline__ int tile_id_of(int x, int y, int tw) {
@@ -222,6 +227,10 @@ struct FView {
 #ifndef VGA_CSTAT
 #define VGA_CSTAT 0          // diagnostic build: phase C's undecided cells counted by word items, masks and mask rounds
                              // (in the slots of vga_c_scan, vga_b_row_cycles, vga_b_cell_cycles, vga_hard_runs: profiles/vga_cstages_ab.txt)
+                             // 2: the certain misses, and those a row-word summary (a) or an 8 x 8 tile-block summary (b)
+                             // of the cell would have proved (vga_b_row_cycles, vga_b_cell_cycles, vga_hard_runs; run
+                             // with DMX_VGA_CCERT=0: profiles/vga_ccert_ab.txt).  The count of (b) is taken on grids of
+                             // two row words a tile row only (65 to 128 tiles across, as 1000^2); it stays 0 elsewhere
 #endif
 #ifndef VGA_HINTS
 #define VGA_HINTS 4          // hint slots a cell (narrow grids with the masks): the hint + VGA_HINTS - 1 fully seen
@@ -391,6 +400,20 @@ __device__ __forceinline__ bool run_hits_fs(const FView& V, Run ru) {
     }
 }
 
+// Row word w of a tile-visibility row or of Fsr (tile row w / wr, tile columns 64 (w % wr) ..) by blocks of 8 x 8 tiles:
+// a bit a byte of the word, the 8 bits placed at block bit (ty >> 3) * nbc + (w % wr) * 8 of a 256-bit summary (word
+// wd; hi: the bits that cross into word wd + 1).  Both sides of phase C's miss certificate are built with it.
+__device__ __forceinline__ void blk_place(unsigned long long t, int w, int wr, int nbc, int& wd, unsigned long long& lo,
+                                          unsigned long long& hi) {
+    unsigned v = 0u;
+#pragma unroll
+    for (int i = 0; i < 8; i++) v |= (unsigned)(((t >> (8 * i)) & 0xFFull) != 0ull) << i;
+    const int p = ((w / wr) >> 3) * nbc + (w % wr) * 8, sh = p & 63;
+    wd = p >> 6;
+    lo = (unsigned long long)v << sh;
+    hi = sh > 56 ? (unsigned long long)v >> (64 - sh) : 0ull;
+}
+
 struct TileShared {
     int src, qn, hn, item, bn;
     int q2n, b2n;         // phase B in stages: entries of the second queue (B1 -> B2), the cell stage's cursor
@@ -401,6 +424,8 @@ struct TileShared {
     unsigned long long cnt, mass;
     unsigned long long mcorr, mdisc;   // merge pass: pairs discovered together, partners of U_f joined
     long long m_f, m_u, disc, target;  // the level loop's state (in LDS: no VGPRs live across the levels)
+    unsigned long long fblk[4];        // Fsr by 8 x 8 blocks of tiles, in tvblk's layout (rebuilt by every level
+                                       // bookkeeping): the frontier's side of phase C's miss certificate
 };
 
 // Next work item: one grid counter (progress and cancel ride on it).  Contiguous per-XCD ranges, so that an
@@ -633,7 +658,11 @@ __device__ __forceinline__ void crow_load(const VgaTileParams& P, const unsigned
     for (int k = 0; k < 4; k++) {
         const int w = k * 64 + lane;
         const unsigned long long fs = Fsr[min(w, tvw - 1)];
+#if VGA_CSTAT == 2
+        const int off = w < tvw ? w * 8 : tvw * 8;   // (diagnostic build: the whole row, for the summaries it counts)
+#else
         const int off = (w < tvw && fs != 0ull && ((nzb >> k) & 1u)) ? w * 8 : tvw * 8;
+#endif
         r.t[k] = buf_load64(rt, off);
         r.f[k] = buf_load64(rf, off);
     }
@@ -682,12 +711,45 @@ __device__ __forceinline__ bool pmask_hit_rows(const VgaTileParams& P, const uns
         how = 1;
         return true;
     }
-    if (__ballot((cw[0] | cw[1] | cw[2] | cw[3]) != 0ull) == 0ull) { how = 2; return false; }
+    if (__ballot((cw[0] | cw[1] | cw[2] | cw[3]) != 0ull) == 0ull) {
+#if VGA_CSTAT == 2
+        if (rstat) {
+            // diagnostic build (profiles/vga_ccert_ab.txt): would a 4-word summary of the cell have proved this miss?
+            // (a) a bit a row word: the word is non-zero, against Fsr's word being non-zero; (b) a bit an 8 x 8 block
+            // of tiles, against the same reduction of Fsr (two words a tile row only: a block row is the 8 lanes
+            // 16g + 2i + word, reduced by three shuffles)
+            bool ma = false, mb = false;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int w = k * 64 + lane;
+                const unsigned long long fs = w < tvw ? Fsr[min(w, tvw - 1)] : 0ull;
+                ma |= r.t[k] != 0ull && fs != 0ull;
+                unsigned cb = 0u, fb = 0u;
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    cb |= (unsigned)(((r.t[k] >> (8 * i)) & 0xFFull) != 0ull) << i;
+                    fb |= (unsigned)(((fs >> (8 * i)) & 0xFFull) != 0ull) << i;
+                }
+#pragma unroll
+                for (int sft = 2; sft <= 8; sft <<= 1) {
+                    cb |= __shfl_xor(cb, sft);
+                    fb |= __shfl_xor(fb, sft);
+                }
+                mb |= (cb & fb) != 0u;
+            }
+            rstat[0] += 1u;
+            rstat[1] += __ballot(ma) == 0ull;
+            rstat[2] += wr == 2 && __ballot(mb) == 0ull;
+        }
+#endif
+        how = 2;
+        return false;
+    }
     how = 0;
 #if VGA_PHASEC_ROWSONLY
     return false;   // attribution build: no mask loads (results differ)
 #endif
-#if VGA_CSTAT
+#if VGA_CSTAT == 1
     if (rstat) {   // diagnostic build: the undecided cell's word items and the masks they could load
         rstat[0] += __popcll(__ballot((cw[0] != 0ull))) + __popcll(__ballot((cw[1] != 0ull))) +
                     __popcll(__ballot((cw[2] != 0ull))) + __popcll(__ballot((cw[3] != 0ull)));
@@ -710,7 +772,7 @@ __device__ __forceinline__ bool pmask_hit_rows(const VgaTileParams& P, const uns
             constexpr int NM = 4;   // masks a lane keeps in flight (2: +1 %, 8: +34 %, round 4)
             unsigned long long mk[NM];
             int tl[NM], sl[NM];
-#if VGA_CSTAT
+#if VGA_CSTAT == 1
             if (rstat) rstat[2]++;   // (a mask round: a dependent trip)
 #endif
 #pragma unroll
@@ -1644,7 +1706,7 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                     const int cn = min(CCH, hn - it0);
                     const int myv = lane < cn ? L[it0 + lane] : -1;
                     // the chunk's non-zero row summaries (tvnz), one load: lane 4j + k holds word k of entry j
-                    static_assert(!VGA_TVNZ || CCH * 4 <= 64, "tvnz prefetch: 4 summary words an entry");
+                    static_assert(CCH * 4 <= 64, "summary prefetch: 4 words an entry");
                     unsigned long long nzp = ~0ull;
                     if (VGA_TVNZ && !FG && P.tvnz) {
                         const int jj = lane >> 2, kk = lane & 3, tvsw = (P.tvw + 63) >> 6;
@@ -1652,6 +1714,24 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                         if (jj < cn && kk < tvsw) nzp = P.tvnz[(size_t)(vj < 0 ? -1 - vj : vj) * tvsw + kk];
                     }
                     unsigned long long certain_m = 0ull, pruned_m = 0ull;   // bit j: chunk entry j
+                    // The miss certificate: the chunk's block summaries in one load, lane 4j + k
+                    // word k of entry j.  A cell none of whose blocks of tiles holds a frontier tile (fblk, the same
+                    // reduction of Fsr) has tvis & Fsr zero: today's certain miss, found without the cell's rows.
+                    // One-sided: a cell it keeps is tested as before.  Entries past cn and special entries (their in-set
+                    // includes Extra) are never rejected.  Not on the HBM frontier, not without the masks.
+                    int ncert = 0;
+                    if (!VGA_PHASEC_OFF && !FG && P.ccert && P.tvblk && P.pmask) {
+                        // (the lane from mbcnt, as lanes_below: values derived from the kernel's `lane` are hoisted and
+                        // held in registers through every phase, which phase B's loops paid for with scratch reloads)
+                        const int ln = lanes_below(~0ull);
+                        const int jj = ln >> 2, kk = ln & 3;
+                        const int vj = __shfl(myv, jj);
+                        unsigned long long cb = 0ull;
+                        if (jj < cn && vj >= 0) cb = P.tvblk[(size_t)vj * 4 + kk];
+                        const unsigned long long meet = __ballot((cb & S.fblk[kk]) != 0ull);
+                        pruned_m = __ballot(ln < cn && myv >= 0 && ((meet >> (4 * (ln & 15))) & 0xFull) == 0ull);
+                        ncert = __popcll(pruned_m);
+                    }
                     if (P.tvis && (!P.pmask || (FG && VGA_WIDE_ROWPASS && P.tvsum))) {   // (wide grids: a row pass in front of the masks)
                         for (int j = 0; j < cn; j += 2) {
                             const int v0 = __builtin_amdgcn_readlane(myv, j);
@@ -1736,6 +1816,11 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                     // entries, the wide path and the run scan take the loop below.
                     const bool c1 = !VGA_PHASEC_OFF && !FG && (P.csplit & 1) && P.pmask;
                     const unsigned long long stm = c1 ? __ballot(lane < cn && myv >= 0) & ~(certain_m | pruned_m) : 0ull;
+                    if (ncert) {   // counted as the certain misses they are (and as the row stage's cells where it runs)
+                        cf_n += ncert;
+                        cf_prun += ncert;
+                        if (c1) c1n += ncert;
+                    }
                     if (stm) {
                         const C1Out co = c1_chunk(P, F, Fsr, Hn, SC, myv, stm, nzp, use_nz);
                         found_m |= co.found;
@@ -1744,7 +1829,7 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                         cf_cert += co.cert;
                         cf_prun += co.prun;
                         cf_hit += __popcll(co.found);
-                        c1n = __popcll(stm);
+                        c1n += __popcll(stm);
                     }
                     for (int j = 0; j < cn; j++) {
                         if (((certain_m | pruned_m | stm) >> j) & 1ull) continue;
@@ -1847,6 +1932,7 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                         if (cf_hit) ST(1, cf_hit);
 #if !VGA_ROWSTAT && !VGA_CSTAT
                         if (c1n) ST(22, c1n);
+                        if (ncert) ST(26, ncert);
 #endif
                     }
                 }
@@ -1949,6 +2035,7 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
             // publish nothing (the merge pass may have set bits anywhere).
             const bool have_list = level > 0;
             for (int i = tid; i < nfs; i += NT) Fsr[i] = 0ull;
+            if (tid < 4) S.fblk[tid] = 0ull;
             if (have_list)
                 for (int t = tid; t < nt; t += NT) F[t] = 0ull;
             __syncthreads();
@@ -2140,6 +2227,19 @@ __global__ void __launch_bounds__(NT) vga_tile_kernel(const VgaTileParams* __res
                 }
             }
             sync_global();
+            // Fsr is final (walk and merge pass are behind the barrier): its reduction to 8 x 8 blocks of tiles, the
+            // frontier's side of phase C's miss certificate (cleared with Fsr above), a thread a non-zero word.  The two
+            // barriers below stand before the next level reads it.
+            if (!FG && P.tvblk && tid < P.th * wr) {
+                const unsigned long long fw = Fsr[tid];
+                if (fw) {
+                    int wd;
+                    unsigned long long lo, hi;
+                    blk_place(fw, tid, wr, (tw + 7) >> 3, wd, lo, hi);
+                    atomicOr(&S.fblk[wd], lo);
+                    if (hi) atomicOr(&S.fblk[min(wd + 1, 3)], hi);
+                }
+            }
             const long long cnt = uni64(S.cnt), mass = uni64(S.mass);
             const long long mcorr = uni64(S.mcorr), mdisc = uni64(S.mdisc);
             if (tid == 0) { const unsigned long long n = __builtin_amdgcn_s_memtime(); ST(12, n - tmark); tmark = n; }
@@ -2494,6 +2594,35 @@ __global__ void tile_vsum_kernel(int64_t Ct, int tvw, const unsigned long long* 
         const unsigned long long bits = __ballot(w < tvw && row[w] != 0ull);
         if (lane == 0) tvsum[(size_t)c * tvsw + j] = bits;
     }
+}
+
+// The view of a cell by 8 x 8 blocks of tiles (grids up to 256 row words with the masks: tvblk, 4 words a cell): bit
+// (ty >> 3) * nbc + (tx >> 3) is set iff the cell sees a tile of that block.  One wave per cell: every lane places its
+// row words' bytes (blk_place), the words are OR-reduced over the wave.
+__global__ void tile_vblk_kernel(int64_t Ct, int tvw, int wr, int nbc, const unsigned long long* tvis, unsigned long long* tvblk) {
+    const int lane = threadIdx.x & 63;
+    const int64_t c = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (c >= Ct) return;
+    const unsigned long long* row = tvis + (size_t)c * tvw;
+    unsigned long long a0 = 0ull, a1 = 0ull, a2 = 0ull, a3 = 0ull;
+    for (int w = lane; w < tvw; w += 64) {
+        const unsigned long long t = row[w];
+        if (t == 0ull) continue;
+        int wd;
+        unsigned long long lo, hi;
+        blk_place(t, w, wr, nbc, wd, lo, hi);
+        a0 |= wd == 0 ? lo : 0ull;
+        a1 |= wd == 1 ? lo : (wd == 0 ? hi : 0ull);
+        a2 |= wd == 2 ? lo : (wd == 1 ? hi : 0ull);
+        a3 |= wd == 3 ? lo : (wd == 2 ? hi : 0ull);
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        a0 |= __shfl_xor(a0, off);
+        a1 |= __shfl_xor(a1, off);
+        a2 |= __shfl_xor(a2, off);
+        a3 |= __shfl_xor(a3, off);
+    }
+    if (lane < 4) tvblk[(size_t)c * 4 + lane] = lane == 0 ? a0 : lane == 1 ? a1 : lane == 2 ? a2 : a3;
 }
 
 // Lattice segment: cells (x0 + p*dx, y0 + p*dy), p = 0..len-1 (dx in {0,1}, dy in {-1,0,1}).

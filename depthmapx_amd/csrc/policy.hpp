@@ -44,6 +44,12 @@ constexpr int kVgaTileBSplit = 3;
 // (Bit 1 is kept for a mask stage, which is not built: the hook masks it off.)  Like DMX_VGA_BSPLIT a correctness
 // switch for tests and bisecting: timings are taken against the parent build.  Hook: DMX_VGA_CSPLIT (0 / 1).
 constexpr int kVgaTileCSplit = 1;
+// phase C's miss certificate ("a miss certificate in front of the rows"): a chunk of hard cells
+// loads the cells' block summaries (tvblk: the cell's view by 8 x 8 blocks of tiles, 4 words a cell) in one trip and
+// drops the cells none of whose blocks holds a frontier tile: certain misses, found without their rows.  0 turns the
+// test off and leaves the summaries in place.  A correctness switch for tests and bisecting: timings are
+// taken against the parent build.  Hook: DMX_VGA_CCERT (0 / 1), read at launch.
+constexpr int kVgaTileCCert = 1;
 // the tile walks of a level (phase A, the level bookkeeping, X = F & ~V) take VGA_WALK_NF tiles a thread at once, all
 // their loads in flight before the first is used, and a plain source builds its level 1 in place (DESIGN.md section 2,
 // "tile walks").  0 selects the loops that take a tile at a time.  A correctness switch for tests and bisecting, not

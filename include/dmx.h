@@ -93,7 +93,9 @@ int dmx_ctx_last_timing(dmx_ctx* ctx, double* makegraph_s, double* vga_s);
  * else the side of the LDS window), [47] makeGraph: the depths at which the map's inexact world coordinates take
  * some diagonal cell out of the diagonal bin in the reference (0: none; see dmx_makegraph), [48] VGA tile search: the
  * longest list of tiles holding an unvisited cell that a level's walks took in the launch, [49] its hard cells that
- * went through phase C's row stage (0 under DMX_VGA_CSPLIT=0 and where the stage does not apply).  n <= 50. */
+ * went through phase C's row stage (0 under DMX_VGA_CSPLIT=0 and where the stage does not apply), [50] its hard cells
+ * that phase C's miss certificate rejected before their rows were read (counted in [13] and [17] as well; 0 under
+ * DMX_VGA_CCERT=0, with the frontier in HBM and without the masks).  n <= 51. */
 int dmx_ctx_last_stats(dmx_ctx* ctx, int64_t* out, int n);
 
 /* The sources the last makeGraph swept a second time (graph node indices, in the order the passes listed
